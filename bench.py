@@ -9,12 +9,24 @@ A "step" is one full Soft-IntroVAE iteration of soft_intro_vae/train_soft_intro_
 8 decoder forwards, both backwards, both Adam updates) on a synthetic U[0,1) NCHW batch already resident in
 HBM, fp32, random-init weights of the CelebA-HQ-256 network (channels [64,128,256,512,512,512], z 512).
 Data-parallel runs (N > 1) report the BASELINE configuration as it is stated — global batch 128 split per image over the
-N GPUs (128/N images per GPU, "scaling": "strong") — as the headline `value`, and ALSO time the fixed-per-GPU-work
-variant (128 images per GPU, global batch 128*N) in the same invocation, reported under "weak"; each names its
-per-GPU batch.  `--scaling strong|weak` runs just one of them.  Gradients of the encoder and of the decoder are each
-all-reduced once per iteration over RCCL (two flat fp32 buffers, 109.5 MB + 83.8 MB).
+N GPUs (128/N images per GPU, "scaling": "strong") — as the headline `value`; with --full (or `--scaling both`) they
+ALSO time the fixed-per-GPU-work variant (128 images per GPU, global batch 128*N) in the same invocation, reported under
+"weak"; each names its per-GPU batch.  `--scaling strong|weak` runs just one of them.  Gradients of the encoder and of
+the decoder are each all-reduced once per iteration over RCCL (two flat fp32 buffers, 109.5 MB + 83.8 MB).
 
-Prints ONE JSON line (rank 0). Besides the contract keys it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, `--warmup` iterations, `--steps`
+timed iterations (no per-launch instrumentation), the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = wall milliseconds of one timed iteration, `config`).
+
+--dump-outputs DIR writes what the last timed iteration produced, as float32 .npy files (inputs are seeded, so two builds
+run with the same arguments compare output for output; at most ~25 MB):
+  stats.npy           the iteration's 8 statistics, in engine.STAT_NAMES order (lossE, lossD, loss_rec, kl_real, ...)
+  fake.npy            the D-step's generated images (whole if <= 2**21 values, else a fixed seeded sample of 2**21 of them)
+  encoder_params.npy  the encoder's flat fp32 weights after the iteration's Adam update (same sampling rule)
+  decoder_params.npy  the decoder's, likewise
+
+--full measures everything else as well, in the same process (several minutes at the default workload).  The line then
+also carries
   roofline      the dominant MFMA kernel timed with HIP events around every launch in the timed region.  `achieved` /
                 `frac` are PHYSICAL: FLOPs the kernel issued to the matrix pipe (Winograd F(2x2,3x3) issues 16/36 of a
                 3x3 conv's multiplies) / measured time, against the dense peak of the dtype (157.3 TFLOP/s fp32 MFMA,
@@ -24,9 +36,9 @@ Prints ONE JSON line (rank 0). Besides the contract keys it carries
                 `step` carries the whole-iteration figures (13 F_E + 19 F_D - 3 f_conv0 per image)
   cpu_baseline  the CPU oracle (oracle/sivae_oracle.py, a torch-CPU restatement pinned to the reference by
                 golden vectors) timed on this host's cores on a bounded sample of the same workload.
-  value_untimed the same workload re-timed in the same process WITHOUT the per-launch HIP events (`value` is the
-                instrumented run the roofline object comes from: ~1 % slower in fp32, ~5 % in bf16 mode)
-  also          (N = 1, default invocation) the other BASELINE.json configurations and the per-GPU shards of the
+  value_untimed the same workload re-timed in the same process WITHOUT the per-launch HIP events (under --full `value` is
+                the instrumented run the roofline object comes from: ~1 % slower in fp32, ~5 % in bf16 mode)
+  also          (N = 1, --full at the default workload) the other BASELINE.json configurations and the per-GPU shards of the
                 data-parallel ones, each measured in this same process: celeb256 at the 16-image shard (config 4 on 8
                 GPUs), soft_intro_vae_bootstrap at batch 64 and at its 8-image shard (config 5), cifar10 batch 256
                 (config 2), celeb128 batch 128 in bf16 mode (config 3, with its HBM fraction), and the bf16 mode at the
@@ -225,10 +237,24 @@ def _pmc_traffic(kernel_key, config, dtype):
     return None
 
 
-def measure(args, cfg, gbatch, world, rank, dev, scaling, steps=None, warmup=None, untimed_steps=0):
+DUMP_SAMPLE = 1 << 21  # values per --dump-outputs array above which a fixed seeded sample of this many is written
+
+
+def _dump_array(t, seed):
+    """float32 host copy of `t` for --dump-outputs: whole when it holds <= DUMP_SAMPLE values, else the values at DUMP_SAMPLE
+    positions drawn from a generator seeded with `seed` (the same positions in every run of the same shape)"""
+    t = t.detach()
+    if t.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def measure(args, cfg, gbatch, world, rank, dev, scaling, steps=None, warmup=None, untimed_steps=0, outputs=False):
     """build a fresh model + engine for `gbatch` images over `world` ranks, run warm-up + timed steps
     -> dict(dt, per, stats, timer_summary); untimed_steps > 0: a second region of that many steps without the per-launch
-    HIP events (dt_untimed)"""
+    HIP events (dt_untimed); outputs: also the host copies of what the last timed step produced (--dump-outputs)"""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     from sivae_hip import dp, ops, rng
@@ -258,7 +284,7 @@ def measure(args, cfg, gbatch, world, rank, dev, scaling, steps=None, warmup=Non
 
     for _ in range(warmup):
         eng.soft_intro_step(real)
-    no_timing = args.no_kernel_timing
+    no_timing = args.no_kernel_timing or not args.full  # (per-launch HIP events only feed --full's roofline object)
     if args.hip_graph:
         if world > 1:
             raise SystemExit("--hip-graph is single-GPU")
@@ -281,6 +307,11 @@ def measure(args, cfg, gbatch, world, rank, dev, scaling, steps=None, warmup=Non
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     timer, ops.TIMER = ops.TIMER, None
+    outs = None
+    if outputs:
+        # before any further step: the images and the statistics the last timed step returned, the weights it left
+        outs = {"stats": _dump_array(last["stats"], 0), "fake": _dump_array(last["fake"], 1),
+                "encoder_params": _dump_array(opt_e.flat, 2), "decoder_params": _dump_array(opt_d.flat, 3)}
     dt_untimed = None
     if untimed_steps > 0:
         torch.cuda.synchronize()
@@ -308,7 +339,7 @@ def measure(args, cfg, gbatch, world, rank, dev, scaling, steps=None, warmup=Non
     torch.cuda.empty_cache()
     return dict(dt=dt, per=per, gbatch=gbatch, stats=stats, summ=summ, sync_bn=sync_bn, scaling=scaling, gamma_r=gr,
                 steps=steps, dt_untimed=dt_untimed, untimed_steps=untimed_steps,
-                paired=os.environ.get("SIVAE_PAIR_PASSES", "auto") != "0")
+                paired=os.environ.get("SIVAE_PAIR_PASSES", "auto") != "0", outputs=outs)
 
 
 def also_legs(args, world, rank, dev):
@@ -366,22 +397,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="celeb256", choices=sorted(CONFIGS))
     ap.add_argument("--global-batch", type=int, default=None, help="override the global batch")
-    ap.add_argument("--scaling", default="both", choices=["both", "weak", "strong"],
+    ap.add_argument("--scaling", default=None, choices=["both", "weak", "strong"],
                     help="strong: the config's batch is the GLOBAL batch (BASELINE config 4: 128 over N GPUs); weak: "
-                         "the config's batch PER GPU; both (default): strong is the headline value, weak is reported "
-                         "beside it (identical runs for N = 1)")
+                         "the config's batch PER GPU; both: strong is the headline value, weak is reported beside it "
+                         "(identical runs for N = 1).  Default: both with --full, else strong")
     ap.add_argument("--bootstrap", action="store_true", help="soft_intro_vae_bootstrap variant (config 5)")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="fp32: the parity path (headline); bf16: config 3's build-defined mode (bf16 storage + bf16 MFMA "
                          "convs, fp32 accumulation / statistics / master weights)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: per-launch kernel timing and the roofline "
+                         "object, the CPU baseline, the untimed re-run of the headline, the other configurations / shard "
+                         "sizes (`also`), the weak-scaling line of N > 1 runs.  Off: only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration produced to DIR/<name>.npy (float32; see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-iters", type=int, default=2)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: short thread sweep, the best count is used")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="(--full) no per-launch HIP events, no roofline object")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the `also` object (the other configurations / shard sizes measured in the same process) and "
-                         "the untimed re-run of the headline")
+                    help="(--full) skip the `also` object (the other configurations / shard sizes measured in the same "
+                         "process) and the untimed re-run of the headline")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--same-device", action="store_true",
                     help="testing only: every rank uses cuda:0 (with --backend gloo) to exercise the DP path on one GPU")
@@ -394,6 +431,8 @@ def main():
                     help="re-execute the two D-step decoder forwards whose inputs and weights are unchanged since the "
                          "E-step (the reference does); default: replay them from the E-step's activations")
     args = ap.parse_args()
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "strong"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as plain `python bench.py --gpus N` (the shape of the N = 1 command): become the launcher — one process
@@ -433,9 +472,10 @@ def main():
             runs.append(("strong", base))
         if args.scaling in ("both", "weak"):
             runs.append(("weak", base * world))
-    headline_run = (world == 1 and args.config == "celeb256" and not args.bootstrap and args.dtype == "fp32"
+    headline_run = (args.full and world == 1 and args.config == "celeb256" and not args.bootstrap and args.dtype == "fp32"
                     and not args.global_batch and not args.hip_graph and not args.no_kernel_timing and not args.no_also)
-    results = [measure(args, cfg, gb, world, rank, dev, sc, untimed_steps=8 if (headline_run and i == 0) else 0)
+    results = [measure(args, cfg, gb, world, rank, dev, sc, untimed_steps=8 if (headline_run and i == 0) else 0,
+                       outputs=bool(args.dump_outputs) and rank == 0 and i == 0)
                for i, (sc, gb) in enumerate(runs)]
     also = also_legs(args, world, rank, dev) if headline_run else None
     if rank != 0:
@@ -519,8 +559,9 @@ def main():
                    "decoder_forward_reuse": not args.no_reuse, "hip_graph": bool(args.hip_graph),
                    "batchnorm": "sync" if head["sync_bn"] else "local",
                    "final_stats": stats},
-        "roofline": roof,
     }
+    if args.full:
+        out["roofline"] = roof
     if head["dt_untimed"]:
         out["value_untimed"] = round(gbatch * head["untimed_steps"] / head["dt_untimed"], 3)
         out["value_untimed_note"] = ("%d further iterations of the same engine without the per-launch HIP events; `value` "
@@ -537,7 +578,7 @@ def main():
                              "ms_per_step": round(1e3 * r["dt"] / args.steps, 3), "global_batch": r["gbatch"],
                              "per_gpu_batch": r["per"], "scaling": r["scaling"],
                              "algorithmic_tflops_per_gpu": round(flops_img * r["gbatch"] * args.steps / r["dt"] / 1e12 / world, 2)}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_batch, args.cpu_iters, args.cpu_threads)
         out["cpu_baseline"]["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
     if also is not None:
@@ -550,6 +591,11 @@ def main():
             "bootstrap256_bs8_shard_img_s": also["bootstrap256_fp32_bs8_shard"]["value"],
             "rate_vs_bs64": also["bootstrap256_fp32_bs8_shard"]["rate_vs_bs64"],
             **{k + "_img_s": also[k]["value"] for k in also if k.startswith(("cifar10", "celeb128", "celeb256_bf16"))}}
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in head["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     print(json.dumps(out))
 
 

@@ -158,8 +158,8 @@ def test_train_entry_point_under_two_process_launch(tmp_path):
 
 
 def test_bench_two_rank_launch_reports_strong_and_weak_lines(tmp_path):
-    """the driver's multi-GPU launch shape on one device: `torch.distributed.run --nproc-per-node 2 bench.py --gpus 2`
-    (gloo, both ranks on cuda:0 — the box has one GPU) prints ONE JSON line whose headline is the BASELINE configuration
+    """the driver's multi-GPU launch shape on one device: `torch.distributed.run --nproc-per-node 2 bench.py --gpus 2
+    --full` (gloo, both ranks on cuda:0 — the box has one GPU) prints ONE JSON line whose headline is the BASELINE configuration
     as stated (global batch 128 split over the ranks: 64 images per GPU, "strong") and which carries the
     fixed-per-GPU-work variant beside it (128 images per GPU, "weak"); the two flat-gradient all-reduces per iteration
     ran (finite losses on the all-reduced gradients)."""
@@ -168,7 +168,7 @@ def test_bench_two_rank_launch_reports_strong_and_weak_lines(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONDONTWRITEBYTECODE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend",
-           "gloo", "--same-device", "--steps", "2", "--warmup", "1"]
+           "gloo", "--same-device", "--full", "--steps", "2", "--warmup", "1"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -5,7 +5,7 @@
 #   tests            full `pytest -m gpu` (tail in tests.txt)
 #   tests:<expr>     `pytest -m gpu -k <expr>`
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's bench invocation (--gpus 1 --steps 20 --warmup 5) -> bench_default_invocation.json
+#   bench            the full bench (--full --gpus 1 --steps 20 --warmup 5) -> bench_default_invocation.json
 #   bench:<name>:<bench.py flags>     any other bench line -> bench_<name>.json
 #   stats:<name>:<bench.py flags>     rocprofv3 --kernel-trace --stats of bench.py <flags> -> kernel_stats_<name>.csv
 #   pmc              HBM traffic (FETCH_SIZE / WRITE_SIZE in separate passes) + matrix-pipe busy of tools/pmc_step.py
@@ -40,7 +40,7 @@ for job in "$@"; do
     bench)
       if [ -z "$name" ]; then
         SECONDS=0
-        timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_default_invocation.json" 2> "$O/bench.err"
+        timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_default_invocation.json" 2> "$O/bench.err"
         echo "bench wall ${SECONDS}s"; line "$O/bench_default_invocation.json"
       else
         timeout 600 python bench.py $flags > "$O/bench_$name.json" 2> "$O/bench_$name.err"; echo "[$name]"; line "$O/bench_$name.json"

@@ -19,10 +19,10 @@ OUT=${SCALE_OUT:-gpurun_out/scale}; mkdir -p "$OUT"
 for N in 1 2 4 8; do
   [ "$N" -le "$NGPU" ] || continue
   if [ "$N" -eq 1 ]; then
-    python bench.py --gpus 1 --steps $STEPS --warmup $WARM --no-cpu-baseline --no-also "${EXTRA[@]}" > "$OUT/n$N.json" 2> "$OUT/n$N.err"
+    python bench.py --full --gpus 1 --steps $STEPS --warmup $WARM --no-cpu-baseline --no-also "${EXTRA[@]}" > "$OUT/n$N.json" 2> "$OUT/n$N.err"
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-      bench.py --gpus $N --steps $STEPS --warmup $WARM "${EXTRA[@]}" > "$OUT/n$N.json" 2> "$OUT/n$N.err"
+      bench.py --full --gpus $N --steps $STEPS --warmup $WARM "${EXTRA[@]}" > "$OUT/n$N.json" 2> "$OUT/n$N.err"
   fi
 done
 python - "$OUT" <<'PY'
