@@ -850,6 +850,13 @@ def bn_stats(x, running_mean=None, running_var=None, num_batches_tracked=None, e
 SYNC_BN = None
 
 
+def stats_rows_fit_segments(rows, B, nseg):
+    """can `rows` conv-epilogue statistics rows of B images (image order: a row is a pixel tile of one image, or a whole
+    number of images) be cut into nseg segments of B / nseg images without a row straddling two of them?"""
+    per_row = B // rows if rows < B else 1
+    return not (rows % nseg or (rows < B and B % rows) or (rows >= B and rows % B) or (B // nseg) % per_row)
+
+
 def bn_stats_from_conv(partials, B, C, HW, running_mean=None, running_var=None, num_batches_tracked=None,
                        eps=1e-5, momentum=0.1, nseg=1, seg_rev=False):
     """nseg > 1: B = nseg * B_seg images, rows of `partials` in image order; -> mean, invstd of nseg * C entries
@@ -861,8 +868,7 @@ def bn_stats_from_conv(partials, B, C, HW, running_mean=None, running_var=None, 
         # a partial row covers a pixel tile of ONE image, or — image pairs on 16 x 16 maps, several images per tile on the
         # 8 x 8 / 4 x 4 maps — a whole number of images: it must never straddle two segments (their statistics would mix)
         rows = partials.shape[0]
-        per_row = B // rows if rows < B else 1
-        if rows % nseg or (rows < B and B % rows) or (rows >= B and rows % B) or (B // nseg) % per_row:
+        if not stats_rows_fit_segments(rows, B, nseg):
             raise ValueError("sivae_hip: %d statistics rows of %d images cannot be cut into %d segments" % (rows, B, nseg))
     if nseg > 1 and SYNC_BN is not None:
         raise RuntimeError("sivae_hip: segmented batches and synchronised BatchNorm do not combine")

@@ -143,6 +143,13 @@ def test_bf16_celeb128_config_vs_fp32_oracle():
     assert not _bf16_vs_oracle(3, 256, [64, 128, 256, 512, 512], 128, 8, hp, seed=1)
 
 
+def test_bf16_celeb256_config_vs_fp32_oracle():
+    """the 256x256 six-level network of celeb256_bf16_bs128 (channels [64,128,256,512,512,512], z 512; the
+    hyper-parameters of test_e2e_gpu.test_celeb256_full_config_vs_oracle) at B = 8, the batch of the 128x128 test"""
+    hp = dict(beta_rec=0.5, beta_kl=1.0, beta_neg=1024.0, gamma_r=1e-8)
+    assert not _bf16_vs_oracle(3, 512, [64, 128, 256, 512, 512, 512], 256, 8, hp, seed=2)
+
+
 def test_fp32_path_untouched_by_bf16_switch():
     """an fp32 iteration, a bf16 iteration, then the same fp32 iteration on a fresh model: bit-identical to the first"""
     from sivae_hip.nn import set_compute_dtype
