@@ -4,8 +4,11 @@ Every function takes contiguous fp32 ROCm-device tensors, allocates the outputs,
 current HIP stream and returns immediately (stream-async). CPU tensors are rejected loudly: the
 product path has no CPU fallback.
 """
+import collections
 import ctypes
+import functools
 import os
+import sys
 
 import torch
 
@@ -54,17 +57,15 @@ class KernelTimer:
 TIMER = None  # set to a KernelTimer() to instrument conv2d_fwd / conv2d_wgrad launches
 
 
-def conv_fwd_kernel_key(ks, Co, pro):
-    """name of the template instantiation sivae_conv2d_fwd dispatches to (mirrors conv_fwd.hip)"""
-    tile = {3: ("1,2,1,4,8,3", "2,2,1,4,2,3", "2,2,2,2,2,2"), 1: ("1,2,1,4,32,1", "2,2,1,4,16,1", "2,2,2,2,16,1"),
-            5: ("1,2,1,4,4,4", "2,2,1,4,4,4", "2,2,2,2,4,3")}[ks][0 if Co <= 32 else (1 if Co <= 64 else 2)]
-    return "conv_fwd_kernel<%d,%s,%s>" % (ks, tile, "true" if pro else "false")
+def timer_begin():
+    """start event of an instrumented launch, or None (no timer installed: the only cost of an untimed launch)"""
+    return TIMER.begin() if TIMER is not None else None
 
 
-def conv_wgrad_kernel_key(ks, Co, pro):
-    tile = {3: "3,1,1,2,2,3", 1: "1,2,2,2,2,1",
-            5: ("1,1,1,1,2,2" if Co <= 32 else "1,1,1,2,1,2")}[ks]
-    return "conv_wgrad_kernel<%d,%s,%s>" % (ks, tile, "true" if pro else "false")
+def timer_end(t0, key, flops, ratio=None):
+    """close the record `timer_begin` opened (call it under `if t0 is not None`); ratio = (numerator, denominator) of
+    executed over algorithmic FLOPs where they differ"""
+    TIMER.end(key, flops, t0, executed=None if ratio is None else flops * ratio[0] / ratio[1])
 
 
 def u8_to_f32(src, flip=None, nhwc=False, scale=1.0 / 255.0):
@@ -194,33 +195,6 @@ def bn_fused_check():
         raise RuntimeError(msg)
 
 
-def _bn_bwd_fused_ok(x, nseg):
-    if not BN_FUSED or SYNC_BN is not None or x.dim() != 4:
-        return False
-    if os.environ.get("SIVAE_DP_SAME_DEVICE", "0") == "1":
-        return False  # several ranks share this GPU (tests only): their persistent grids could starve each other
-    B, C, H, W = x.shape
-    return _lib.load().sivae_bn_bwd_fused_supported(B, C, H, W, B // nseg) == 1
-
-
-def _bn_bwd_fused(dy, y, mask, x, mean, invstd, gamma, beta, act_mode, slope, dx, dz, dgamma, dbeta, dy_pooled, dz_sum,
-                  nseg):
-    B, C, H, W = x.shape
-    L = _lib.load()
-    ws = workspace(L.sivae_bn_bwd_fused_workspace_bytes(B, C, H, W, B // nseg), x.device)
-    try:
-        _lib.call("sivae_bn_bwd_fused", _p(dy), _p(y), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta),
-                  int(act_mode), float(slope), _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)),
-                  int(bool(dz_sum)), B // nseg, _p(bn_fused_state(x.device)), _p(ws), ws.numel(), _s(x))
-    except _lib.SivaeError as e:
-        if e.code != -2:
-            raise
-        # a shape the plan of this variant does not take after all (the query and the launch plan with the same
-        # register budget since round 5, so this is a safety net): the three-launch form takes every shape
-        _bn_bwd_seg(dy, y, mask, x, mean, invstd, gamma, beta, act_mode, slope, dx, dz, dgamma, dbeta, dy_pooled, dz_sum,
-                    nseg)
-
-
 def _out(out, shape, device):
     """a caller-provided destination (a contiguous fp32 device tensor of exactly `shape`: the parameter-gradient slab
     views of optim.FlatAdam) or a fresh tensor"""
@@ -274,25 +248,16 @@ def pack_wino(w, mode):
 # SIVAE_WINO=0 keeps every 3x3 conv on the direct implicit-GEMM kernel (A/B measurements, debugging)
 WINO = os.environ.get("SIVAE_WINO", "1") != "0"
 WINO_UP = os.environ.get("SIVAE_WINO_UP", "1") != "0"  # phase-decomposed F(2x2,2x2) kernel for conv-after-upsample
+WINO_WGRAD = os.environ.get("SIVAE_WINO_WGRAD", os.environ.get("SIVAE_WINO", "1")) != "0"
 # Winograd F(4x4,3x3) for the large-map 3x3 convs without a fused prologue (SIVAE_WINO4=0: F(2x2,3x3) everywhere);
 # SIVAE_WINO4_MAXC: largest channel count it takes (its U slab per 64-channel tile is 2.25x the F(2x2,3x3) one)
 WINO4 = os.environ.get("SIVAE_WINO4", "1") != "0"
+WINO4_MAXC = int(os.environ.get("SIVAE_WINO4_MAXC", "512"))
 # SIVAE_WINO4_B6: the F(4x4,3x3) forward / data gradient on the bf16 matrix pipe with fp32-exact products (six bf16 MFMAs
 # per fp32 product, conv_wino4_b6.hip) for layers with at least SIVAE_WINO4_B6_MINC input channels; 0: the fp32-MFMA kernel
 WINO4_B6 = os.environ.get("SIVAE_WINO4_B6", "0") != "0"
 WINO4_B6_MINC = int(os.environ.get("SIVAE_WINO4_B6_MINC", "16"))
 WINO4_B6_PRO = os.environ.get("SIVAE_WINO4_B6_PRO", "1") != "0"
-
-
-def _w4_key(b6, pro, sup):
-    """KernelTimer key = the kernel rocprofv3 names: conv_wino4_kernel<PRO>, or conv_wino4_grid_kernel<PRO> on 8x8 / 4x4 maps"""
-    p = "true" if pro is not None else "false"
-    return ("conv_wino4_b6_kernel<%s>" if b6 else ("conv_wino4_grid_kernel<%s>" if sup >= 3 else "conv_wino4_kernel<%s>")) % p
-
-
-def wino4_b6_takes(Ci, pro):
-    return WINO4_B6 and Ci >= WINO4_B6_MINC and (pro is None or WINO4_B6_PRO)
-WINO4_MAXC = int(os.environ.get("SIVAE_WINO4_MAXC", "512"))
 # F(4x4,3x3) weight gradient (conv_wino4_wgrad.hip); SIVAE_WINO4_WGRAD=0: the F(2x2,3x3) one everywhere
 WINO4_WGRAD = WINO4 and os.environ.get("SIVAE_WINO4_WGRAD", "1") != "0"
 # SIVAE_WINO4_FORCE=1: take the F(4x4,3x3) kernels wherever they are SUPPORTED, not only where they pay (tests: the
@@ -312,7 +277,6 @@ WINO4_PRO = os.environ.get("SIVAE_WINO4_PRO", "1") != "0"  # ... also with a fus
 # 256x256 bs128 (593 vs 585 ms per iteration: the extra tensor read sits on the kernel's critical path and disables its
 # next-item prefetch, which costs more than the 14 ms reduction pass it removes) -> off by default.
 FUSE_BN_BWD = os.environ.get("SIVAE_FUSE_BN_BWD", "0") == "1"
-WINO_WGRAD = os.environ.get("SIVAE_WINO_WGRAD", os.environ.get("SIVAE_WINO", "1")) != "0"
 # streaming kernel for the 1x1 convs (SIVAE_CONV1_STREAM=0: the LDS-tiled direct kernel)
 CONV1_STREAM = os.environ.get("SIVAE_CONV1_STREAM", "1") != "0"
 # merged-contraction kernel for the 5x5 convs from <= 3 into <= 64 channels (SIVAE_CONV5_K75=0: the direct kernel)
@@ -419,6 +383,258 @@ def space_to_depth2(x):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ routes
+# WHICH kernel a convolution or BatchNorm backward gets is decided here, from integers and flags alone: the module
+# switches above (read at call time) and library predicates, which need no device.  The launch functions below only
+# allocate and marshal what the route names.  tests/test_conv_routes_host.py holds the routes of the benchmarked
+# networks to a recording of the previous dispatch; a new kernel path is a new Route value here and nothing else.
+#   family       kernel family (k75 / stream1x1 / wino4 / wino4_splitk / wino4_b6 / wino_up / wino / wino_splitk / direct ...)
+#   entry        the C entry point
+#   operand      the PackedW method that builds the weight operand (None: the caller's direct pack, or no weight)
+#   args         which optional arguments `entry` takes (_conv_call)
+#   materialise  the upsampled input (BatchNorm: the pooled dy) is expanded by a launch of its own first
+#   split        split-K factor
+#   stats_rows   rows of the BatchNorm statistics partials the epilogue writes (asked for with want_stats only)
+#   ws_bytes     scratch the entry point needs
+#   key, ratio   KernelTimer key (the kernel rocprofv3 names) and executed / algorithmic FLOPs as (numerator, denominator)
+#   error        (exception type, message) of a combination that is refused
+Route = collections.namedtuple("Route", "family entry operand args materialise split stats_rows ws_bytes key ratio error",
+                               defaults=(None, "", False, 1, 0, 0, None, None, None))
+_F44, _F22, _F22_UP = (36.0, 144.0), (16.0, 36.0), (9.0, 36.0)  # multiplies per output: F(4x4,3x3), F(2x2,3x3), F(2x2,2x2)
+_routes = {}
+
+
+def _memo(route_fn):
+    """A conv route depends on its arguments, the module switches and library predicates that are fixed for the process:
+    computed once per layer shape (four predicate calls and a key string, about 4 us, on every launch otherwise — the
+    small-batch iterations are bound by host time per launch).  `_SwitchWatch` below empties the memo whenever an
+    attribute of this module is assigned, which is how tests and tools flip switches."""
+    @functools.wraps(route_fn)
+    def cached(*sizes, **flags):
+        k = (route_fn, sizes, tuple(flags.items()))
+        r = _routes.get(k)
+        if r is None:
+            r = _routes[k] = route_fn(*sizes, **flags)
+        return r
+    return cached
+
+
+def _tf(flag):
+    return "true" if flag else "false"
+
+
+def conv_fwd_kernel_key(ks, Co, pro):
+    """name of the template instantiation sivae_conv2d_fwd dispatches to (mirrors conv_fwd.hip)"""
+    tile = {3: ("1,2,1,4,8,3", "2,2,1,4,2,3", "2,2,2,2,2,2"), 1: ("1,2,1,4,32,1", "2,2,1,4,16,1", "2,2,2,2,16,1"),
+            5: ("1,2,1,4,4,4", "2,2,1,4,4,4", "2,2,2,2,4,3")}[ks][0 if Co <= 32 else (1 if Co <= 64 else 2)]
+    return "conv_fwd_kernel<%d,%s,%s>" % (ks, tile, _tf(pro))
+
+
+def conv_wgrad_kernel_key(ks, Co, pro):
+    tile = {3: "3,1,1,2,2,3", 1: "1,2,2,2,2,1",
+            5: ("1,1,1,1,2,2" if Co <= 32 else "1,1,1,2,1,2")}[ks]
+    return "conv_wgrad_kernel<%d,%s,%s>" % (ks, tile, _tf(pro))
+
+
+def _wino_key(W, pro):
+    return "conv_wino_kernel<%s,%s>" % ("1,4" if W >= 32 else ("2,3" if W >= 16 else ("2,2" if W == 8 else "1,1")), _tf(pro))
+
+
+def _w4_key(b6, pro, sup):
+    """conv_wino4_kernel<PRO>, or conv_wino4_grid_kernel<PRO> on 8x8 / 4x4 maps"""
+    return ("conv_wino4_b6_kernel<%s>" if b6 else
+            ("conv_wino4_grid_kernel<%s>" if sup >= 3 else "conv_wino4_kernel<%s>")) % _tf(pro)
+
+
+def wino4_b6_takes(Ci, pro):
+    return WINO4_B6 and Ci >= WINO4_B6_MINC and (not pro or WINO4_B6_PRO)
+
+
+@_memo
+def conv2d_fwd_route(B, Ci, Co, H, W, ks, *, packed=True, mode=0, bias=False, pro=False, upsample=False,
+                     want_stats=False, has_out=False, accumulate=False, nseg=1):
+    """route of conv2d_fwd for a [B, Ci] input and a [B, Co, H, W] OUTPUT map (packed: wp is a PackedW of that mode)"""
+    L = _lib.load()
+    if (CONV5_K75 and ks == 5 and packed and not pro and not upsample and not accumulate and not has_out
+            and L.sivae_conv5_k75_supported(Ci, Co) == 1):
+        # the encoder stem / the data gradient of Decoder.predict: whole contraction (K = 75) merged; 64 output rows x 76
+        # contraction columns are issued
+        return Route("k75", "sivae_conv5_k75_fwd", "k75", "bS", key="conv5_k75_kernel", ratio=(64.0 * 76, Co * Ci * 25.0),
+                     stats_rows=L.sivae_conv5_k75_num_px_tiles(B, H, W) if want_stats else 0)
+    if (CONV1_STREAM and ks == 1 and not bias and not pro and not upsample and not want_stats
+            and L.sivae_conv1x1_stream_supported(B, Ci, Co, H * W) == 1):
+        # ResidualBlock.conv_expand (forward / data gradient): x streamed straight into the MFMA operand
+        return Route("stream1x1", "sivae_conv1x1_stream", "direct" if packed else None, "fa", key="conv1x1_stream_kernel")
+    sup = L.sivae_conv2d_wino4_supported(H, W) if (WINO and WINO4) else 0
+    if sup > 2 and not (WINO4_SMALL and (WINO4_SMALL_FORCE or L.sivae_conv2d_wino4_small_pays(B, Ci, Co, H, W) == 1)):
+        sup = 0  # (8x8 / 4x4 maps: only where the image-grid launch beats F(2x2,3x3) — few items or short K slices do not)
+    # an upsampled input: the phase-form kernels (conv_wino_up.hip) cover the maps from 32x32 up; on the 16x16 / 8x8 outputs
+    # of the deep decoder blocks (Decoder res_in_16 / res_in_8, train_soft_intro_vae.py:153-158) the upsampled tensor is a
+    # few MB — materialise it (one small launch) and take the F(4x4,3x3) image-grid kernel instead of F(2x2,3x3)
+    if (sup and ks == 3 and not bias and packed and 16 <= Ci and max(Ci, Co) <= WINO4_MAXC
+            and (not upsample or (sup >= 2 and WINO4_UP_SMALL and not pro))
+            # (maps up to 16x16: whole image grids per work item, inside one segment)
+            and (B // nseg) % L.sivae_conv2d_wino4_images_per_item(H, W) == 0
+            and (not pro or (WINO4_PRO and nseg * ((Ci + 31) // 32) * 32 <= 1024))):
+        pays = L.sivae_conv2d_wino4_pays(B, Ci, Co, H, W) == 1
+        # fewer work items than CUs (the deep layers of a per-GPU shard): split over K when that fills the chip
+        S = L.sivae_conv2d_wino4_splitk(B, Ci, Co, H, W) if (WINO4_SPLITK and not pays) else 1
+        b6 = wino4_b6_takes(Ci, pro) and sup <= 2
+        if S > 1:
+            return Route("wino4_splitk", "sivae_conv2d_wino4_b6_fwd_splitk" if b6 else "sivae_conv2d_wino4_fwd_splitk",
+                         "wino4_b6" if b6 else "wino4", "PSagw", upsample, S, B if want_stats else 0,  # (rows per image)
+                         L.sivae_conv2d_wino4_splitk_workspace_bytes(B, Ci, Co, H, W), _w4_key(b6, pro, sup), _F44)
+        if pays or WINO4_FORCE:
+            # large maps: F(4x4,3x3) — 2.25 multiplies per output pixel instead of 4
+            entry, args = (("sivae_conv2d_wino4_b6_fwd", "PSag") if b6 else
+                           (("sivae_conv2d_wino4_fwd_pro", "PSag") if pro else ("sivae_conv2d_wino4_fwd", "Sa")))
+            return Route("wino4_b6" if b6 else "wino4", entry, "wino4_b6" if b6 else "wino4", args, upsample,
+                         stats_rows=L.sivae_conv2d_wino4_num_px_tiles(B, H, W) if want_stats else 0,
+                         key=_w4_key(b6, pro, sup), ratio=_F44)
+    wino = WINO and ks == 3 and not bias and packed and L.sivae_conv2d_wino_supported(H, W) == 1
+    if nseg > 1 and (pro or want_stats) and not wino:
+        return Route("direct", "sivae_conv2d_fwd", error=(
+            ValueError, "sivae_hip: a segmented batch needs the Winograd 3x3 kernels for fused BatchNorm work"))
+    if wino and WINO_UP and upsample and not accumulate and mode == 0 and L.sivae_conv2d_wino_up_supported(H, W) == 1:
+        if nseg > 1 and pro:
+            return Route("wino_up", "sivae_conv2d_wino_up_fwd", error=(
+                ValueError, "sivae_hip: no segmented prologue in the upsample-phase kernel"))
+        return Route("wino_up", "sivae_conv2d_wino_up_fwd", "wino_up", "PS", ratio=_F22_UP,
+                     key="conv_wino_up_kernel<%s,%s>" % ("1,4" if W >= 64 else "2,3", _tf(pro)),
+                     stats_rows=L.sivae_conv2d_wino_up_num_px_tiles(B, H, W) if want_stats else 0)
+    if wino:
+        # split-K for launches that would leave most of the chip idle (deep small maps at small batch)
+        S = L.sivae_conv2d_wino_splitk(B, Ci, Co, H, W)
+        seg = "_seg" if nseg > 1 else ""
+        if S > 1:
+            return Route("wino_splitk", "sivae_conv2d_wino_fwd_splitk" + seg, "wino", "PSuagw" if seg else "PSuaw", split=S,
+                         stats_rows=L.sivae_conv2d_wino_splitk_stats_rows(B, Ci, Co, H, W) if want_stats else 0,
+                         ws_bytes=L.sivae_conv2d_wino_splitk_workspace_bytes(B, Ci, Co, H, W), key=_wino_key(W, pro),
+                         ratio=_F22)
+        return Route("wino", "sivae_conv2d_wino_fwd" + seg, "wino", "PSuag" if seg else "bPSua", key=_wino_key(W, pro),
+                     ratio=_F22, stats_rows=L.sivae_conv2d_wino_num_px_tiles(B, H, W) if want_stats else 0)
+    return Route("direct", "sivae_conv2d_fwd", "direct" if packed else None, "bPSkua", key=conv_fwd_kernel_key(ks, Co, pro),
+                 stats_rows=L.sivae_conv2d_fwd_num_px_tiles(B, Co, H, W) if want_stats else 0)
+
+
+@_memo
+def conv2d_wgrad_route(B, Ci, Co, H, W, ks, *, pro=False, upsample=False, nseg=1):
+    """route of conv2d_wgrad for dy [B, Co, H, W] (x at half resolution with upsample)"""
+    L = _lib.load()
+    if (WINO_WGRAD and WINO_UP and upsample and ks == 3 and not pro
+            and L.sivae_conv2d_wino_up_wgrad_supported(H // 2, W // 2) == 1):
+        # conv after nearest-2x upsample: phase-form F(2x2,2x2) weight gradient on the low-resolution x
+        return Route("wino_up_wgrad", "sivae_conv2d_wino_up_wgrad", None, "hw", key="wino_up_wgrad_kernel", ratio=_F22_UP,
+                     ws_bytes=L.sivae_conv2d_wino_up_wgrad_workspace_bytes(B, Ci, Co, H // 2, W // 2))
+    ips = L.sivae_conv2d_wino4_wgrad_images_per_stage(H, W) if ks == 3 else 0  # (8x8 / 4x4 maps: 2 / 4 images per strip)
+    # (an upsampled x on the 16x16 / 8x8 maps, which the phase-form weight gradient above does not take: materialised, as
+    # in conv2d_fwd_route)
+    if (WINO4_WGRAD and WINO_WGRAD and ks == 3 and (not pro or nseg <= 2)
+            and (not upsample or (WINO4_UP_SMALL and not pro and H <= 16 and W <= 16))
+            and max(Ci, Co) <= WINO4_MAXC and ips > 0 and (B // nseg) % ips == 0 and (ips == 1 or WINO4_SMALL)
+            and (L.sivae_conv2d_wino4_wgrad_pays(B, Ci, Co, H, W) == 1 or (WINO4_FORCE and min(Ci, Co) >= 16))):
+        # Winograd F(4x4,3x3) weight gradient (conv_wino4_wgrad.hip): 36 instead of 64 multiplies per tile, co, ci
+        return Route("wino4_wgrad", "sivae_conv2d_wino4_wgrad", None, "Pgw", upsample, ratio=_F44,
+                     ws_bytes=L.sivae_conv2d_wino4_wgrad_workspace_bytes(B, Ci, Co, H, W),
+                     key="wino4_wgrad_kernel<%s,%s>" % (_tf(pro), _tf(ips > 1)))
+    if WINO_WGRAD and ks == 3 and L.sivae_conv2d_wino_wgrad_supported(H, W) == 1:
+        seg = nseg > 1 and pro
+        return Route("wino_wgrad", "sivae_conv2d_wino_wgrad_seg" if seg else "sivae_conv2d_wino_wgrad", None,
+                     "Pugw" if seg else "Puw", ws_bytes=L.sivae_conv2d_wino_wgrad_workspace_bytes(B, Ci, Co, H, W),
+                     key="wino_wgrad_kernel<%s,1>" % _tf(pro), ratio=_F22)
+    if nseg > 1 and pro:
+        return Route("direct_wgrad", "sivae_conv2d_wgrad", error=(
+            ValueError, "sivae_hip: a segmented batch needs the Winograd weight-gradient kernel for a fused prologue"))
+    return Route("direct_wgrad", "sivae_conv2d_wgrad", None, "Pkuw", key=conv_wgrad_kernel_key(ks, Co, pro),
+                 ws_bytes=L.sivae_conv2d_wgrad_workspace_bytes(B, Ci, Co, H, W, ks))
+
+
+@_memo
+def conv2d_up_dgrad_route(B, C, N, H, W, *, has_wp1=False):
+    """route of conv2d_up_dgrad for dy [B, C, H, W] -> dx [B, N, H/2, W/2]; the operand of the wino4_pool family is built
+    from the mode-1 PackedW (wp1), the others from the mode-0 one"""
+    L = _lib.load()
+    if (WINO4_DGRAD_POOL and WINO4 and has_wp1 and max(C, N) <= WINO4_MAXC
+            and L.sivae_conv2d_wino4_dgrad_pool_pays(B, C, N, H, W) == 1):
+        return Route("wino4_pool", "sivae_conv2d_wino4_dgrad_pool", "wino4", "a", key="conv_wino4_pool_kernel<false>",
+                     ratio=_F44)
+    key = "conv_wino_up_dgrad_kernel<%s>" % ("1,4" if W // 2 >= 32 else "2,3")
+    S = L.sivae_conv2d_wino_up_dgrad_splitk(B, C, N, H // 2, W // 2)
+    if S > 1:  # small shards: split the 4C input planes
+        return Route("wino_up_dgrad_splitk", "sivae_conv2d_wino_up_dgrad_splitk_run", "wino_up_dgrad", "haw", split=S,
+                     ws_bytes=L.sivae_conv2d_wino_up_dgrad_splitk_workspace_bytes(B, C, N, H // 2, W // 2), key=key,
+                     ratio=_F22_UP)
+    return Route("wino_up_dgrad", "sivae_conv2d_wino_up_dgrad", "wino_up_dgrad", "ha", key=key, ratio=_F22_UP)
+
+
+def bn_bwd_route(B, C, H, W, *, op="bn_bwd", four_d=True, dy_pooled=False, nseg=1):
+    """route of bn_bwd / bn_bwd_signmask / bn_bwd_dzsum (op: "bn_bwd", "signmask", "dzsum") for x [B, C, H, W] (four_d
+    False: x is [B, C] or flat, H * W elements per channel and image).  Three tiers: the one-launch persistent kernel,
+    the segmented / fused-finalize form, the plain form of `op`."""
+    L = _lib.load()
+    sync = SYNC_BN is not None
+    # (shapes / modes the fused read of a pooled dy does not cover: the pool's adjoint runs first)
+    expand = op == "bn_bwd" and dy_pooled and (sync or bool(H & 1) or bool(W & 3))
+    if (BN_FUSED and not sync and four_d
+            # several ranks share this GPU (tests only): their persistent grids could starve each other
+            and os.environ.get("SIVAE_DP_SAME_DEVICE", "0") != "1"
+            and L.sivae_bn_bwd_fused_supported(B, C, H, W, B // nseg) == 1):
+        return Route("bn_fused", "sivae_bn_bwd_fused", materialise=expand,
+                     ws_bytes=L.sivae_bn_bwd_fused_workspace_bytes(B, C, H, W, B // nseg))
+    if nseg > 1 or (BN_FUSED_FINALIZE and not sync and four_d):
+        if sync:
+            return Route("bn_seg", "sivae_bn_bwd_seg", materialise=expand, error=(
+                RuntimeError, "sivae_hip: segmented batches and synchronised BatchNorm do not combine"))
+        return Route("bn_seg", "sivae_bn_bwd_seg", materialise=expand,
+                     ws_bytes=L.sivae_bn_workspace_bytes(B // nseg, nseg * C, H * W))
+    ws = L.sivae_bn_workspace_bytes(B, C, H * W)
+    if op != "bn_bwd":
+        return Route("bn_" + op, "sivae_bn_bwd_" + op, ws_bytes=ws)
+    if sync:
+        return Route("bn_sync", "sivae_bn_bwd_reduce", materialise=expand, ws_bytes=ws)
+    if dy_pooled and not expand:
+        return Route("bn_pooled_dy", "sivae_bn_bwd_pooled_dy", ws_bytes=ws)
+    return Route("bn_plain", "sivae_bn_bwd", materialise=expand, ws_bytes=ws)
+
+
+def _prologue(pro):
+    """pro = (mean, invstd, gamma, beta, slope) of a fused producer BatchNorm + LeakyReLU, or None -> the five C arguments"""
+    if pro is None:
+        return None, None, None, None, 1.0
+    pm, pi, pg, pb, slope = pro
+    _require(pm, pi, pg, pb)
+    return _p(pm), _p(pi), _p(pg), _p(pb), float(slope)
+
+
+def _conv_call(r, a, b, c, dims, ks=0, bias=None, pro=None, stats=None, upsample=False, accumulate=False, seg=0):
+    """the one launch of a conv route.  Every conv entry point takes a subset of the same arguments in the same order —
+    three tensors, [b]ias, [P]rologue + slope, [S]tatistics, the five sizes ([h]: the map halved, [f]: H * W as one),
+    [k]ernel size, [u]psample flag, [a]ccumulate flag, se[g]ment images, [w]orkspace + its size, stream — and r.args
+    names the subset."""
+    s = r.args
+    args = [_p(a), _p(b), _p(c)]
+    if "b" in s:
+        args.append(_p(bias))
+    if "P" in s:
+        args.extend(_prologue(pro))
+    if "S" in s:
+        args.append(_p(stats))
+    B, Ci, Co, H, W = dims
+    args.extend((B, Ci, Co, H // 2, W // 2) if "h" in s else ((B, Ci, Co, H * W) if "f" in s else dims))
+    if "k" in s:
+        args.append(ks)
+    if "u" in s:
+        args.append(int(bool(upsample)))
+    if "a" in s:
+        args.append(int(bool(accumulate)))
+    if "g" in s:
+        args.append(seg)
+    if "w" in s:
+        ws = workspace(r.ws_bytes, a.device)
+        args.extend((_p(ws), ws.numel()))
+    _lib.call(r.entry, *args, _s(a))
+
+
 def conv2d_dgrad_bnbwd_supported(H, W):
     return WINO and FUSE_BN_BWD and SYNC_BN is None and _lib.load().sivae_conv2d_wino_supported(H, W) == 1
 
@@ -428,16 +644,14 @@ def conv2d_dgrad_bnbwd(dy, wp, Cm, bn_x, mean, invstd, gamma, beta, slope=LRELU_
     h = LeakyReLU(BN(bn_x)): -> (dh, partials [n_tiles, Cm, 2])"""
     _require(dy, bn_x, mean, invstd, gamma, beta)
     B, Ci, H, W = dy.shape
-    L = _lib.load()
     dh = torch.empty((B, Cm, H, W), dtype=torch.float32, device=dy.device)
-    part = torch.empty((L.sivae_conv2d_wino_num_px_tiles(B, H, W), Cm, 2), dtype=torch.float32, device=dy.device)
-    t0 = TIMER.begin() if TIMER is not None else None
+    part = torch.empty((_lib.load().sivae_conv2d_wino_num_px_tiles(B, H, W), Cm, 2), dtype=torch.float32,
+                       device=dy.device)
+    t0 = timer_begin()
     _lib.call("sivae_conv2d_wino_dgrad_bnbwd", _p(dy), _p(wp.wino()), _p(dh), _p(bn_x), _p(mean), _p(invstd), _p(gamma),
               _p(beta), float(slope), _p(part), B, Ci, Cm, H, W, _s())
     if t0 is not None:
-        flops = 2.0 * B * H * W * Cm * Ci * 9
-        TIMER.end("conv_wino_kernel<%s,false>" % ("1,4" if W >= 32 else ("2,3" if W >= 16 else ("2,2" if W == 8 else "1,1"))),
-                  flops, t0, executed=flops * 16.0 / 36.0)
+        timer_end(t0, _wino_key(W, False), 2.0 * B * H * W * Cm * Ci * 9, _F22)
     return dh, part
 
 
@@ -465,30 +679,13 @@ def conv2d_up_dgrad(dy, wp, N, out=None, accumulate=False, wp1=None):
     launches with N <= 64 take the F(4x4,3x3) kernel with the 2x2 block sum folded into its output transform)."""
     _require(dy, out)
     B, C, H, W = dy.shape
-    Hs, Ws = H // 2, W // 2
-    dx = out if out is not None else torch.empty((B, N, Hs, Ws), dtype=torch.float32, device=dy.device)
-    assert dx.shape == (B, N, Hs, Ws)
-    t0 = TIMER.begin() if TIMER is not None else None
-    L = _lib.load()
-    if (WINO4_DGRAD_POOL and WINO4 and wp1 is not None and max(C, N) <= WINO4_MAXC
-            and L.sivae_conv2d_wino4_dgrad_pool_pays(B, C, N, H, W) == 1):
-        assert dx.is_contiguous()
-        _lib.call("sivae_conv2d_wino4_dgrad_pool", _p(dy), _p(wp1.wino4()), _p(dx), B, C, N, H, W, int(bool(accumulate)),
-                  _s(dy))
-        if t0 is not None:
-            flops = 2.0 * B * H * W * C * N * 9
-            TIMER.end("conv_wino4_pool_kernel<false>", flops, t0, executed=flops * 36.0 / 144.0)
-        return dx
-    if L.sivae_conv2d_wino_up_dgrad_splitk(B, C, N, Hs, Ws) > 1:  # small shards: split the 4C input planes
-        ws = workspace(L.sivae_conv2d_wino_up_dgrad_splitk_workspace_bytes(B, C, N, Hs, Ws), dy.device)
-        _lib.call("sivae_conv2d_wino_up_dgrad_splitk_run", _p(dy), _p(wp.wino_up_dgrad()), _p(dx), B, C, N, Hs, Ws,
-                  int(bool(accumulate)), _p(ws), ws.numel(), _s(dy))
-    else:
-        _lib.call("sivae_conv2d_wino_up_dgrad", _p(dy), _p(wp.wino_up_dgrad()), _p(dx), B, C, N, Hs, Ws,
-                  int(bool(accumulate)), _s(dy))
+    r = conv2d_up_dgrad_route(B, C, N, H, W, has_wp1=wp1 is not None)
+    dx = _out(out, (B, N, H // 2, W // 2), dy.device)
+    t0 = timer_begin()
+    _conv_call(r, dy, getattr(wp1 if r.family == "wino4_pool" else wp, r.operand)(), dx, (B, C, N, H, W),
+               accumulate=accumulate)
     if t0 is not None:
-        flops = 2.0 * B * H * W * C * N * 9
-        TIMER.end("conv_wino_up_dgrad_kernel<%s>" % ("1,4" if Ws >= 32 else "2,3"), flops, t0, executed=flops * 9.0 / 36.0)
+        timer_end(t0, r.key, 2.0 * B * H * W * C * N * 9, r.ratio)
     return dx
 
 
@@ -504,169 +701,27 @@ def conv2d_fwd(x, wp, Co, ks, bias=None, pro=None, upsample=False, want_stats=Fa
                accumulate=False, nseg=1):
     """x [B, Ci, H, W] (or [B, Ci, H/2, W/2] with upsample) -> y [B, Co, H, W] (+ stats partials).
 
-    wp: a direct pack (tensor from pack_weight) or a PackedW; with a PackedW, 3x3 convs on maps the Winograd
-    kernel supports (even H >= 8, even W >= 16) run sivae_conv2d_wino_fwd.
+    wp: a direct pack (tensor from pack_weight) or a PackedW; with a PackedW the kernel is chosen per call from the
+    layer's sizes (conv2d_fwd_route).
     pro = (mean, invstd, gamma, beta, slope): fused producer BatchNorm + LeakyReLU on load."""
     B, Ci, Hs, Ws = x.shape
     H, W = (2 * Hs, 2 * Ws) if upsample else (Hs, Ws)
-    L = _lib.load()
-    if (CONV5_K75 and ks == 5 and isinstance(wp, PackedW) and pro is None and not upsample and not accumulate
-            and out is None and L.sivae_conv5_k75_supported(Ci, Co) == 1):
-        # the encoder stem / the data gradient of Decoder.predict: whole contraction (K = 75) merged
-        _require(x, bias)
-        y = torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-        stats = (torch.empty((L.sivae_conv5_k75_num_px_tiles(B, H, W), Co, 2), dtype=torch.float32, device=x.device)
-                 if want_stats else None)
-        t0 = TIMER.begin() if TIMER is not None else None
-        _lib.call("sivae_conv5_k75_fwd", _p(x), _p(wp.k75()), _p(y), _p(bias), _p(stats), B, Ci, Co, H, W, _s(x))
-        if t0 is not None:
-            TIMER.end("conv5_k75_kernel", 2.0 * B * H * W * Co * Ci * 25, t0,
-                      executed=2.0 * B * H * W * 64 * 76)  # (64 output rows x 76 contraction columns are issued)
-        return (y, stats) if want_stats else y
-    if (CONV1_STREAM and ks == 1 and bias is None and pro is None and not upsample and not want_stats
-            and L.sivae_conv1x1_stream_supported(B, Ci, Co, H * W) == 1):
-        # ResidualBlock.conv_expand (forward / data gradient): x streamed straight into the MFMA operand
-        wd = wp.direct() if isinstance(wp, PackedW) else wp
-        _require(x, wd, out)
-        y = out if out is not None else torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-        assert y.shape == (B, Co, H, W) and y.is_contiguous()
-        t0 = TIMER.begin() if TIMER is not None else None
-        _lib.call("sivae_conv1x1_stream", _p(x), _p(wd), _p(y), B, Ci, Co, H * W, int(bool(accumulate)), _s(x))
-        if t0 is not None:
-            TIMER.end("conv1x1_stream_kernel", 2.0 * B * H * W * Co * Ci, t0)
-        return y
-    w4_sup = L.sivae_conv2d_wino4_supported(H, W) if (WINO and WINO4) else 0
-    if w4_sup > 2 and not (WINO4_SMALL and (WINO4_SMALL_FORCE or L.sivae_conv2d_wino4_small_pays(B, Ci, Co, H, W) == 1)):
-        w4_sup = 0  # (8x8 / 4x4 maps: only where the image-grid launch beats F(2x2,3x3) — few items or short K slices do not)
-    w4_ipi = L.sivae_conv2d_wino4_images_per_item(H, W) if w4_sup else 1
-    # an upsampled input: the phase-form kernels (conv_wino_up.hip) cover the maps from 32x32 up; on the 16x16 / 8x8 outputs of
-    # the deep decoder blocks (Decoder res_in_16 / res_in_8, train_soft_intro_vae.py:153-158) the upsampled tensor is a
-    # few MB — materialise it (one small launch) and take the F(4x4,3x3) image-grid kernel instead of F(2x2,3x3)
-    w4_up = bool(upsample) and w4_sup >= 2 and WINO4_UP_SMALL and pro is None
-    w4_ok = (w4_sup and ks == 3 and bias is None and (not upsample or w4_up) and isinstance(wp, PackedW)
-             and 16 <= Ci and max(Ci, Co) <= WINO4_MAXC
-             and (B // nseg) % w4_ipi == 0  # (maps up to 16x16: whole image grids per work item, inside one segment)
-             and (pro is None or (WINO4_PRO and nseg * ((Ci + 31) // 32) * 32 <= 1024)))
-    # fewer work items than CUs (the deep layers of a per-GPU shard): split over K when that fills the chip
-    w4_S = (L.sivae_conv2d_wino4_splitk(B, Ci, Co, H, W) if (w4_ok and WINO4_SPLITK
-                                                              and L.sivae_conv2d_wino4_pays(B, Ci, Co, H, W) != 1) else 1)
-    if w4_ok and upsample:
-        if w4_S > 1 or L.sivae_conv2d_wino4_pays(B, Ci, Co, H, W) == 1 or WINO4_FORCE:
-            x, upsample = upsample2_fwd(x), False
-        else:
-            w4_ok = False
-    if w4_ok and w4_S > 1:
-        _require(x, out)
-        y = out if out is not None else torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-        assert y.shape == (B, Co, H, W) and y.is_contiguous()
-        stats = torch.empty((B, Co, 2), dtype=torch.float32, device=x.device) if want_stats else None  # (rows per image)
-        ws = workspace(L.sivae_conv2d_wino4_splitk_workspace_bytes(B, Ci, Co, H, W), x.device)
-        pm = pi = pg = pb = None
-        slope = 1.0
-        if pro is not None:
-            pm, pi, pg, pb, slope = pro
-            _require(pm, pi, pg, pb)
-        t0 = TIMER.begin() if TIMER is not None else None
-        b6 = wino4_b6_takes(Ci, pro) and w4_sup <= 2
-        _lib.call("sivae_conv2d_wino4_b6_fwd_splitk" if b6 else "sivae_conv2d_wino4_fwd_splitk", _p(x),
-                  _p(wp.wino4_b6() if b6 else wp.wino4()), _p(y), _p(pm), _p(pi), _p(pg), _p(pb),
-                  float(slope), _p(stats), B, Ci, Co, H, W, int(bool(accumulate)), (B // nseg) if nseg > 1 else 0,
-                  _p(ws), ws.numel(), _s(x))
-        if t0 is not None:
-            flops = 2.0 * B * H * W * Co * Ci * 9
-            TIMER.end(_w4_key(b6, pro, w4_sup), flops, t0, executed=flops * 36.0 / 144.0)
-        return (y, stats) if want_stats else y
-    if w4_ok and (L.sivae_conv2d_wino4_pays(B, Ci, Co, H, W) == 1 or WINO4_FORCE):
-        # large maps: F(4x4,3x3) — 2.25 multiplies per output pixel instead of 4
-        _require(x, out)
-        y = out if out is not None else torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-        assert y.shape == (B, Co, H, W) and y.is_contiguous()
-        stats = (torch.empty((L.sivae_conv2d_wino4_num_px_tiles(B, H, W), Co, 2), dtype=torch.float32, device=x.device)
-                 if want_stats else None)
-        t0 = TIMER.begin() if TIMER is not None else None
-        b6 = wino4_b6_takes(Ci, pro) and w4_sup <= 2
-        if b6:
-            pm = pi = pg = pb = None
-            slope = 1.0
-            if pro is not None:
-                pm, pi, pg, pb, slope = pro
-                _require(pm, pi, pg, pb)
-            _lib.call("sivae_conv2d_wino4_b6_fwd", _p(x), _p(wp.wino4_b6()), _p(y), _p(pm), _p(pi), _p(pg), _p(pb),
-                      float(slope), _p(stats), B, Ci, Co, H, W, int(bool(accumulate)), (B // nseg) if nseg > 1 else 0,
-                      _s(x))
-        elif pro is not None:
-            pm, pi, pg, pb, slope = pro
-            _require(pm, pi, pg, pb)
-            _lib.call("sivae_conv2d_wino4_fwd_pro", _p(x), _p(wp.wino4()), _p(y), _p(pm), _p(pi), _p(pg), _p(pb),
-                      float(slope), _p(stats), B, Ci, Co, H, W, int(bool(accumulate)), (B // nseg) if nseg > 1 else 0,
-                      _s(x))
-        else:
-            _lib.call("sivae_conv2d_wino4_fwd", _p(x), _p(wp.wino4()), _p(y), _p(stats), B, Ci, Co, H, W,
-                      int(bool(accumulate)), _s(x))
-        if t0 is not None:
-            flops = 2.0 * B * H * W * Co * Ci * 9
-            TIMER.end(_w4_key(b6, pro, w4_sup), flops, t0, executed=flops * 36.0 / 144.0)
-        return (y, stats) if want_stats else y
-    wino = (WINO and ks == 3 and bias is None and isinstance(wp, PackedW)
-            and L.sivae_conv2d_wino_supported(H, W) == 1)
-    wino_up = (wino and WINO_UP and upsample and not accumulate and wp.mode == 0
-               and L.sivae_conv2d_wino_up_supported(H, W) == 1)
-    if isinstance(wp, PackedW):
-        wp = wp.wino_up() if wino_up else (wp.wino() if wino else wp.direct())
-    _require(x, wp, bias, out)
-    y = out if out is not None else torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-    assert y.shape == (B, Co, H, W)
-    # split-K for launches that would leave most of the chip idle (deep small maps at small batch)
-    splitk = wino and not wino_up and L.sivae_conv2d_wino_splitk(B, Ci, Co, H, W) > 1
-    stats = None
-    if want_stats:
-        nt = (L.sivae_conv2d_wino_up_num_px_tiles(B, H, W) if wino_up else
-              (L.sivae_conv2d_wino_splitk_stats_rows(B, Ci, Co, H, W) if splitk else
-               (L.sivae_conv2d_wino_num_px_tiles(B, H, W) if wino else L.sivae_conv2d_fwd_num_px_tiles(B, Co, H, W))))
-        stats = torch.empty((nt, Co, 2), dtype=torch.float32, device=x.device)
-    pm = pi = pg = pb = None
-    slope = 1.0
-    if pro is not None:
-        pm, pi, pg, pb, slope = pro
-        _require(pm, pi, pg, pb)
-    if nseg > 1 and (pro is not None or want_stats) and not (wino or wino_up):
-        raise ValueError("sivae_hip: a segmented batch needs the Winograd 3x3 kernels for fused BatchNorm work")
-    if nseg > 1 and pro is not None and wino_up:
-        raise ValueError("sivae_hip: no segmented prologue in the upsample-phase kernel")
-    t0 = TIMER.begin() if TIMER is not None else None
-    if wino_up:
-        _lib.call("sivae_conv2d_wino_up_fwd", _p(x), _p(wp), _p(y), _p(pm), _p(pi), _p(pg), _p(pb), float(slope),
-                  _p(stats), B, Ci, Co, H, W, _s())
-    elif splitk:
-        ws = workspace(L.sivae_conv2d_wino_splitk_workspace_bytes(B, Ci, Co, H, W), x.device)
-        if nseg > 1:
-            _lib.call("sivae_conv2d_wino_fwd_splitk_seg", _p(x), _p(wp), _p(y), _p(pm), _p(pi), _p(pg), _p(pb),
-                      float(slope), _p(stats), B, Ci, Co, H, W, int(bool(upsample)), int(bool(accumulate)), B // nseg,
-                      _p(ws), ws.numel(), _s())
-        else:
-            _lib.call("sivae_conv2d_wino_fwd_splitk", _p(x), _p(wp), _p(y), _p(pm), _p(pi), _p(pg), _p(pb),
-                      float(slope), _p(stats), B, Ci, Co, H, W, int(bool(upsample)), int(bool(accumulate)), _p(ws),
-                      ws.numel(), _s())
-    elif wino and nseg > 1:
-        _lib.call("sivae_conv2d_wino_fwd_seg", _p(x), _p(wp), _p(y), _p(pm), _p(pi), _p(pg), _p(pb), float(slope),
-                  _p(stats), B, Ci, Co, H, W, int(bool(upsample)), int(bool(accumulate)), B // nseg, _s())
-    elif wino:
-        _lib.call("sivae_conv2d_wino_fwd", _p(x), _p(wp), _p(y), _p(bias), _p(pm), _p(pi), _p(pg), _p(pb),
-                  float(slope), _p(stats), B, Ci, Co, H, W, int(bool(upsample)), int(bool(accumulate)), _s())
-    else:
-        _lib.call("sivae_conv2d_fwd", _p(x), _p(wp), _p(y), _p(bias), _p(pm), _p(pi), _p(pg), _p(pb), float(slope),
-                  _p(stats), B, Ci, Co, H, W, ks, int(bool(upsample)), int(bool(accumulate)), _s())
+    packed = isinstance(wp, PackedW)
+    r = conv2d_fwd_route(B, Ci, Co, H, W, ks, packed=packed, mode=wp.mode if packed else 0, bias=bias is not None,
+                         pro=pro is not None, upsample=bool(upsample), want_stats=want_stats, has_out=out is not None,
+                         accumulate=bool(accumulate), nseg=nseg)
+    _require(x, bias, out, None if packed else wp)
+    if r.error is not None:
+        raise r.error[0](r.error[1])
+    if r.materialise:
+        x, upsample = upsample2_fwd(x), False
+    w = getattr(wp, r.operand)() if packed else wp
+    y = _out(out, (B, Co, H, W), x.device)
+    stats = torch.empty((r.stats_rows, Co, 2), dtype=torch.float32, device=x.device) if want_stats else None
+    t0 = timer_begin()
+    _conv_call(r, x, w, y, (B, Ci, Co, H, W), ks, bias, pro, stats, upsample, accumulate, (B // nseg) if nseg > 1 else 0)
     if t0 is not None:
-        flops = 2.0 * B * H * W * Co * Ci * ks * ks  # algorithmic (reference nn.Conv2d) FLOPs
-        if wino_up:
-            TIMER.end("conv_wino_up_kernel<%s,%s>" % ("1,4" if W >= 64 else "2,3", "true" if pro is not None else "false"),
-                      flops, t0, executed=flops * 9.0 / 36.0)
-        elif wino:
-            key = "conv_wino_kernel<%s,%s>" % ("1,4" if W >= 32 else ("2,3" if W >= 16 else ("2,2" if W == 8 else "1,1")),
-                                               "true" if pro is not None else "false")
-            TIMER.end(key, flops, t0, executed=flops * 16.0 / 36.0)
-        else:
-            TIMER.end(conv_fwd_kernel_key(ks, Co, pro is not None), flops, t0)
+        timer_end(t0, r.key, 2.0 * B * H * W * Co * Ci * ks * ks, r.ratio)  # (algorithmic: the reference nn.Conv2d's FLOPs)
     return (y, stats) if want_stats else y
 
 
@@ -675,76 +730,17 @@ def conv2d_wgrad(x, dy, ks, pro=None, upsample=False, out=None, nseg=1):
     _require(x, dy)
     B, Ci = x.shape[0], x.shape[1]
     _, Co, H, W = dy.shape
-    L = _lib.load()
-    if (WINO_WGRAD and WINO_UP and upsample and ks == 3 and pro is None
-            and L.sivae_conv2d_wino_up_wgrad_supported(H // 2, W // 2) == 1):
-        # conv after nearest-2x upsample: phase-form F(2x2,2x2) weight gradient on the low-resolution x
-        ws = workspace(L.sivae_conv2d_wino_up_wgrad_workspace_bytes(B, Ci, Co, H // 2, W // 2), x.device)
-        dw = _out(out, (Co, Ci, 3, 3), x.device)
-        t0 = TIMER.begin() if TIMER is not None else None
-        _lib.call("sivae_conv2d_wino_up_wgrad", _p(x), _p(dy), _p(dw), B, Ci, Co, H // 2, W // 2, _p(ws), ws.numel(),
-                  _s())
-        if t0 is not None:
-            flops = 2.0 * B * H * W * Co * Ci * 9
-            TIMER.end("wino_up_wgrad_kernel", flops, t0, executed=flops * 9.0 / 36.0)
-        return dw
-    w4g_ips = L.sivae_conv2d_wino4_wgrad_images_per_stage(H, W) if ks == 3 else 0  # (8x8 / 4x4 maps: 2 / 4 images per strip)
-    # (an upsampled x on the 16x16 / 8x8 maps, which the phase-form weight gradient above does not take: materialised, as
-    # in conv2d_fwd)
-    w4g_up = bool(upsample) and WINO4_UP_SMALL and pro is None and H <= 16 and W <= 16
-    if (WINO4_WGRAD and WINO_WGRAD and ks == 3 and (not upsample or w4g_up) and (pro is None or nseg <= 2)
-            and max(Ci, Co) <= WINO4_MAXC and w4g_ips > 0 and (B // nseg) % w4g_ips == 0
-            and (w4g_ips == 1 or WINO4_SMALL)
-            and (L.sivae_conv2d_wino4_wgrad_pays(B, Ci, Co, H, W) == 1
-                 or (WINO4_FORCE and min(Ci, Co) >= 16))):
-        if upsample:
-            x = upsample2_fwd(x)
-        # Winograd F(4x4,3x3) weight gradient (conv_wino4_wgrad.hip): 36 instead of 64 multiplies per tile, co, ci
-        ws = workspace(L.sivae_conv2d_wino4_wgrad_workspace_bytes(B, Ci, Co, H, W), x.device)
-        dw = _out(out, (Co, Ci, 3, 3), x.device)
-        pm = pi = pg = pb = None
-        slope = 1.0
-        if pro is not None:
-            pm, pi, pg, pb, slope = pro
-            _require(pm, pi, pg, pb)
-        t0 = TIMER.begin() if TIMER is not None else None
-        _lib.call("sivae_conv2d_wino4_wgrad", _p(x), _p(dy), _p(dw), _p(pm), _p(pi), _p(pg), _p(pb), float(slope), B, Ci,
-                  Co, H, W, (B // nseg) if (nseg > 1 and pro is not None) else 0, _p(ws), ws.numel(), _s())
-        if t0 is not None:
-            flops = 2.0 * B * H * W * Co * Ci * 9
-            TIMER.end("wino4_wgrad_kernel<%s,%s>" % ("true" if pro is not None else "false",
-                                                     "true" if w4g_ips > 1 else "false"), flops, t0,
-                      executed=flops * 36.0 / 144.0)
-        return dw
-    wino = WINO_WGRAD and ks == 3 and L.sivae_conv2d_wino_wgrad_supported(H, W) == 1
-    nbytes = (L.sivae_conv2d_wino_wgrad_workspace_bytes(B, Ci, Co, H, W) if wino
-              else L.sivae_conv2d_wgrad_workspace_bytes(B, Ci, Co, H, W, ks))
-    ws = workspace(nbytes, x.device)
+    r = conv2d_wgrad_route(B, Ci, Co, H, W, ks, pro=pro is not None, upsample=bool(upsample), nseg=nseg)
+    if r.error is not None:
+        raise r.error[0](r.error[1])
+    if r.materialise:
+        x, upsample = upsample2_fwd(x), False
     dw = _out(out, (Co, Ci, ks, ks), x.device)
-    pm = pi = pg = pb = None
-    slope = 1.0
-    if pro is not None:
-        pm, pi, pg, pb, slope = pro
-        _require(pm, pi, pg, pb)
-    if nseg > 1 and pro is not None and not wino:
-        raise ValueError("sivae_hip: a segmented batch needs the Winograd weight-gradient kernel for a fused prologue")
-    t0 = TIMER.begin() if TIMER is not None else None
-    if wino and nseg > 1 and pro is not None:
-        _lib.call("sivae_conv2d_wino_wgrad_seg", _p(x), _p(dy), _p(dw), _p(pm), _p(pi), _p(pg), _p(pb), float(slope),
-                  B, Ci, Co, H, W, int(bool(upsample)), B // nseg, _p(ws), ws.numel(), _s())
-    elif wino:
-        _lib.call("sivae_conv2d_wino_wgrad", _p(x), _p(dy), _p(dw), _p(pm), _p(pi), _p(pg), _p(pb), float(slope),
-                  B, Ci, Co, H, W, int(bool(upsample)), _p(ws), ws.numel(), _s())
-    else:
-        _lib.call("sivae_conv2d_wgrad", _p(x), _p(dy), _p(dw), _p(pm), _p(pi), _p(pg), _p(pb), float(slope), B, Ci,
-                  Co, H, W, ks, int(bool(upsample)), _p(ws), ws.numel(), _s())
+    t0 = timer_begin()
+    _conv_call(r, x, dy, dw, (B, Ci, Co, H, W), ks, None, pro, None, upsample, False,
+               (B // nseg) if (nseg > 1 and pro is not None) else 0)
     if t0 is not None:  # (includes the tiny slice-reduce launch that follows the MFMA kernel)
-        flops = 2.0 * B * H * W * Co * Ci * ks * ks
-        if wino:
-            TIMER.end("wino_wgrad_kernel<%s,1>" % ("true" if pro is not None else "false"), flops, t0,
-                      executed=flops * 16.0 / 36.0)
-        else:
-            TIMER.end(conv_wgrad_kernel_key(ks, Co, pro is not None), flops, t0)
+        timer_end(t0, r.key, 2.0 * B * H * W * Co * Ci * ks * ks, r.ratio)
     return dw
 
 
@@ -760,10 +756,10 @@ def linear_fwd(x, w, bias=None, relu=False):
     N = w.shape[0]
     ws = workspace(_lib.load().sivae_linear_workspace_bytes(B, K, N), x.device)
     y = torch.empty((B, N), dtype=torch.float32, device=x.device)
-    t0 = TIMER.begin() if TIMER is not None else None
+    t0 = timer_begin()
     _lib.call("sivae_linear_fwd", _p(x), _p(w), _p(bias), _p(y), int(bool(relu)), B, K, N, _p(ws), ws.numel(), _s(x))
     if t0 is not None:
-        TIMER.end("linear_fwd_kernel", 2.0 * B * K * N, t0)
+        timer_end(t0, "linear_fwd_kernel", 2.0 * B * K * N)
     return y
 
 
@@ -773,10 +769,10 @@ def linear_dgrad(dy, w):
     K = w.shape[1]
     ws = workspace(_lib.load().sivae_linear_workspace_bytes(B, K, N), dy.device)
     dx = torch.empty((B, K), dtype=torch.float32, device=dy.device)
-    t0 = TIMER.begin() if TIMER is not None else None
+    t0 = timer_begin()
     _lib.call("sivae_linear_dgrad", _p(dy), _p(w), _p(dx), B, K, N, _p(ws), ws.numel(), _s(dy))
     if t0 is not None:
-        TIMER.end("linear_dgrad_kernel", 2.0 * B * K * N, t0)
+        timer_end(t0, "linear_dgrad_kernel", 2.0 * B * K * N)
     return dx
 
 
@@ -785,10 +781,10 @@ def linear_wgrad(dy, x, out=None):
     B, N = dy.shape
     K = x.shape[1]
     dw = _out(out, (N, K), dy.device)
-    t0 = TIMER.begin() if TIMER is not None else None
+    t0 = timer_begin()
     _lib.call("sivae_linear_wgrad", _p(dy), _p(x), _p(dw), B, K, N, _s(dy))
     if t0 is not None:
-        TIMER.end("linear_wgrad_kernel", 2.0 * B * K * N, t0)
+        timer_end(t0, "linear_wgrad_kernel", 2.0 * B * K * N)
     return dw
 
 
@@ -809,10 +805,10 @@ def conv5_smallco_fwd(x, wq, Co, bias=None):
     _require(x, wq, bias)
     B, Ci, H, W = x.shape
     y = torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-    t0 = TIMER.begin() if TIMER is not None else None
+    t0 = timer_begin()
     _lib.call("sivae_conv5_smallco_fwd", _p(x), _p(wq), _p(y), _p(bias), B, Ci, Co, H, W, _s())
     if t0 is not None:
-        TIMER.end("conv5_smallco_fwd_kernel<9>", 2.0 * B * H * W * Co * Ci * 25, t0)
+        timer_end(t0, "conv5_smallco_fwd_kernel<9>", 2.0 * B * H * W * Co * Ci * 25)
     return y
 
 
@@ -822,10 +818,10 @@ def conv5_edge_wgrad(x, dy, out=None):
     Co = dy.shape[1]
     ws = workspace(_lib.load().sivae_conv5_edge_wgrad_workspace_bytes(B, Ci, Co, H, W), x.device)
     dw = _out(out, (Co, Ci, 5, 5), x.device)
-    t0 = TIMER.begin() if TIMER is not None else None
+    t0 = timer_begin()
     _lib.call("sivae_conv5_edge_wgrad", _p(x), _p(dy), _p(dw), B, Ci, Co, H, W, _p(ws), ws.numel(), _s())
     if t0 is not None:
-        TIMER.end("conv5_edge_wgrad_kernel<%s>" % ("true" if Co <= 3 else "false"), 2.0 * B * H * W * Co * Ci * 25, t0)
+        timer_end(t0, "conv5_edge_wgrad_kernel<%s>" % ("true" if Co <= 3 else "false"), 2.0 * B * H * W * Co * Ci * 25)
     return dw
 
 
@@ -881,14 +877,10 @@ def bn_stats_from_conv(partials, B, C, HW, running_mean=None, running_var=None, 
                   C, HW, float(eps), float(momentum), _p(running_mean), _p(running_var), _p(num_batches_tracked),
                   _p(mean), _p(invstd), _p(ws), ws.numel() if ws is not None else 0, _s())
         return mean, invstd
-    if SYNC_BN is not None:
-        sums = torch.empty((C, 2), dtype=torch.float64, device=partials.device)
-        _lib.call("sivae_bn_sums_from_conv", _p(partials), partials.shape[0], C, _p(sums), _s())
-        world = SYNC_BN(sums)
-        _lib.call("sivae_bn_finalize_sums", _p(sums), C, float(B) * HW * world, float(eps), float(momentum),
-                  _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(mean), _p(invstd), _s())
-        return mean, invstd
-    _lib.call("sivae_bn_stats_from_conv", _p(partials), partials.shape[0], B, C, HW, float(eps), float(momentum),
+    sums = torch.empty((C, 2), dtype=torch.float64, device=partials.device)
+    _lib.call("sivae_bn_sums_from_conv", _p(partials), partials.shape[0], C, _p(sums), _s())
+    world = SYNC_BN(sums)
+    _lib.call("sivae_bn_finalize_sums", _p(sums), C, float(B) * HW * world, float(eps), float(momentum),
               _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(mean), _p(invstd), _s())
     return mean, invstd
 
@@ -969,30 +961,18 @@ def bn_apply_act_signmask(x, res, mean, invstd, gamma, beta, slope=LRELU_SLOPE, 
     return y, yp, mask
 
 
-def _bn_bwd_seg(dy, y, mask, x, mean, invstd, gamma, beta, act_mode, slope, dx, dz, dgamma, dbeta, dy_pooled, dz_sum,
-                nseg):
-    """every BatchNorm-backward variant (local statistics), segmented or not (mean / invstd [nseg][C]), with the
-    per-channel finalize fused into the reduction kernel"""
-    if SYNC_BN is not None:
-        raise RuntimeError("sivae_hip: segmented batches and synchronised BatchNorm do not combine")
+def _bn_bwd_run(op, dy, y, mask, x, mean, invstd, gamma, beta, act_mode, slope, want_dz, dz_sum, dy_pooled,
+                want_param_grads, pg_out, nseg):
+    """the body of bn_bwd / bn_bwd_signmask / bn_bwd_dzsum: route -> allocate -> launch.  -> dx, dz (full resolution, its
+    2x2 block sums with dz_sum, or None), dgamma, dbeta (mean / invstd are [nseg][C])"""
     B, C = x.shape[0], x.shape[1]
     H, W = (x.shape[2], x.shape[3]) if x.dim() == 4 else (1, x.numel() // (B * C))
-    ws = workspace(_lib.load().sivae_bn_workspace_bytes(B // nseg, nseg * C, H * W), x.device)
-    cnt = counters(x.device) if (BN_FUSED_FINALIZE and C <= 8192) else None
-    _lib.call("sivae_bn_bwd_seg", _p(dy), _p(y), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta),
-              int(act_mode), float(slope), _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)),
-              int(bool(dz_sum)), B // nseg, _p(cnt), _p(ws), ws.numel(), _s())
-
-
-def bn_bwd_signmask(dy, mask, x, mean, invstd, gamma, slope=LRELU_SLOPE, dy_pooled=False, dz_sum=False,
-                    want_dz=True, want_param_grads=True, pg_out=None, nseg=1):
-    """backward of bn_apply_act_signmask -> dx, dz (full resolution, or its 2x2 block sums with dz_sum), dgamma,
-    dbeta.  dy_pooled: dy is the gradient of the pooled output."""
-    _require(dy, x, mean, invstd, gamma)
-    B, C, H, W = x.shape
-    if mask.dtype != torch.uint8 or not mask.is_cuda or mask.numel() < _lib.load().sivae_bn_signmask_bytes(B, C, H * W):
-        raise TypeError("sivae_hip: bn_bwd_signmask needs the uint8 device mask bn_apply_act_signmask returned")
-    ws = workspace(_lib.load().sivae_bn_workspace_bytes(B, C, H * W), x.device)
+    r = bn_bwd_route(B, C, H, W, op=op, four_d=x.dim() == 4, dy_pooled=bool(dy_pooled), nseg=nseg)
+    if r.materialise:
+        dy, dy_pooled = avgpool2_bwd(dy, H, W), False
+    _require(dy, y, x, mean, invstd, gamma, beta)
+    if r.error is not None:
+        raise r.error[0](r.error[1])
     dx = torch.empty_like(x)
     dz = None
     if dz_sum:
@@ -1000,18 +980,56 @@ def bn_bwd_signmask(dy, mask, x, mean, invstd, gamma, slope=LRELU_SLOPE, dy_pool
     elif want_dz:
         dz = torch.empty_like(x)
     dgamma, dbeta = _pg(pg_out, C, x.device, want_param_grads)
-    if _bn_bwd_fused_ok(x, nseg):
-        _bn_bwd_fused(dy, None, mask, x, mean, invstd, gamma, None, 3, slope, dx, dz, dgamma, dbeta, dy_pooled, dz_sum,
-                      nseg)
-        return dx, dz, dgamma, dbeta
-    if nseg > 1 or (BN_FUSED_FINALIZE and SYNC_BN is None):
-        _bn_bwd_seg(dy, None, mask, x, mean, invstd, gamma, None, 3, slope, dx, dz, dgamma, dbeta, dy_pooled, dz_sum,
-                    nseg)
-        return dx, dz, dgamma, dbeta
-    _lib.call("sivae_bn_bwd_signmask", _p(dy), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), float(slope), _p(dx),
-              _p(dz), _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)), int(bool(dz_sum)), _p(ws), ws.numel(),
-              _s())
+    ws = workspace(r.ws_bytes, x.device)
+    # (every variant, segmented or not, that the two general entry points take)
+    general = (_p(dy), _p(y), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode), float(slope),
+               _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)), int(bool(dz_sum)), B // nseg)
+    seg = r.family == "bn_seg"
+    if r.family == "bn_fused":
+        try:
+            _lib.call(r.entry, *general, _p(bn_fused_state(x.device)), _p(ws), ws.numel(), _s(x))
+        except _lib.SivaeError as e:
+            if e.code != -2:
+                raise
+            # a shape the plan of this variant does not take after all (the query and the launch plan with the same
+            # register budget since round 5, so this is a safety net): the three-launch form takes every shape
+            seg, ws = True, workspace(_lib.load().sivae_bn_workspace_bytes(B // nseg, nseg * C, H * W), x.device)
+        else:
+            return dx, dz, dgamma, dbeta
+    if seg:  # the per-channel finalize fused into the reduction kernel
+        cnt = counters(x.device) if (BN_FUSED_FINALIZE and C <= 8192) else None
+        _lib.call("sivae_bn_bwd_seg", *general, _p(cnt), _p(ws), ws.numel(), _s())
+    elif r.family == "bn_sync":
+        local = torch.empty((C, 2), dtype=torch.float64, device=x.device)
+        _lib.call(r.entry, _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode), float(slope),
+                  _p(local), B, C, H * W, _p(ws), ws.numel(), _s())
+        glob = local.clone()
+        world = SYNC_BN(glob)
+        _lib.call("sivae_bn_bwd_apply", _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta),
+                  int(act_mode), float(slope), _p(local), _p(glob), float(B) * H * W * world, _p(dx), _p(dz),
+                  _p(dgamma), _p(dbeta), B, C, H * W, _p(ws), ws.numel(), _s())
+    elif r.family == "bn_signmask":
+        _lib.call(r.entry, _p(dy), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), float(slope), _p(dx), _p(dz),
+                  _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)), int(bool(dz_sum)), _p(ws), ws.numel(), _s())
+    elif r.family == "bn_dzsum":
+        _lib.call(r.entry, _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), float(slope), _p(dx), _p(dz),
+                  _p(dgamma), _p(dbeta), B, C, H, W, _p(ws), ws.numel(), _s())
+    else:  # sivae_bn_bwd (sizes B, C, H * W) / sivae_bn_bwd_pooled_dy (B, C, H, W)
+        _lib.call(r.entry, _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode), float(slope),
+                  _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, *((H, W) if dy_pooled else (H * W,)), _p(ws),
+                  ws.numel(), _s())
     return dx, dz, dgamma, dbeta
+
+
+def bn_bwd_signmask(dy, mask, x, mean, invstd, gamma, slope=LRELU_SLOPE, dy_pooled=False, dz_sum=False,
+                    want_dz=True, want_param_grads=True, pg_out=None, nseg=1):
+    """backward of bn_apply_act_signmask -> dx, dz (full resolution, or its 2x2 block sums with dz_sum), dgamma,
+    dbeta.  dy_pooled: dy is the gradient of the pooled output."""
+    B, C, H, W = x.shape
+    if mask.dtype != torch.uint8 or not mask.is_cuda or mask.numel() < _lib.load().sivae_bn_signmask_bytes(B, C, H * W):
+        raise TypeError("sivae_hip: bn_bwd_signmask needs the uint8 device mask bn_apply_act_signmask returned")
+    return _bn_bwd_run("signmask", dy, None, mask, x, mean, invstd, gamma, None, 3, slope, want_dz, dz_sum, dy_pooled,
+                       want_param_grads, pg_out, nseg)
 
 
 def bn_bwd_dzsum_supported(x):
@@ -1021,21 +1039,8 @@ def bn_bwd_dzsum_supported(x):
 def bn_bwd_dzsum(dy, y, x, mean, invstd, gamma, slope=LRELU_SLOPE, want_param_grads=True, pg_out=None, nseg=1):
     """act_mode-1 BatchNorm(+residual+LeakyReLU) backward -> dx, dz_half (2x2 block sums of the residual-branch
     gradient, [B, C, H/2, W/2]), dgamma, dbeta"""
-    _require(dy, y, x, mean, invstd, gamma)
-    B, C, H, W = x.shape
-    ws = workspace(_lib.load().sivae_bn_workspace_bytes(B, C, H * W), x.device)
-    dx = torch.empty_like(x)
-    dzh = torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
-    dgamma, dbeta = _pg(pg_out, C, x.device, want_param_grads)
-    if _bn_bwd_fused_ok(x, nseg):
-        _bn_bwd_fused(dy, y, None, x, mean, invstd, gamma, None, 1, slope, dx, dzh, dgamma, dbeta, False, True, nseg)
-        return dx, dzh, dgamma, dbeta
-    if nseg > 1 or (BN_FUSED_FINALIZE and SYNC_BN is None):
-        _bn_bwd_seg(dy, y, None, x, mean, invstd, gamma, None, 1, slope, dx, dzh, dgamma, dbeta, False, True, nseg)
-        return dx, dzh, dgamma, dbeta
-    _lib.call("sivae_bn_bwd_dzsum", _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), float(slope), _p(dx), _p(dzh),
-              _p(dgamma), _p(dbeta), B, C, H, W, _p(ws), ws.numel(), _s())
-    return dx, dzh, dgamma, dbeta
+    return _bn_bwd_run("dzsum", dy, y, None, x, mean, invstd, gamma, None, 1, slope, False, True, False,
+                       want_param_grads, pg_out, nseg)
 
 
 def bn_bwd(dy, y, x, mean, invstd, gamma, slope=LRELU_SLOPE, want_dz=False, want_param_grads=True, beta=None,
@@ -1045,43 +1050,8 @@ def bn_bwd(dy, y, x, mean, invstd, gamma, slope=LRELU_SLOPE, want_dz=False, want
     dy_pooled: dy is the gradient of AvgPool2d(2)(output) at half resolution; the pool's adjoint is applied on load."""
     if act_mode is None:
         act_mode = 1 if y is not None else 0
-    if dy_pooled and (SYNC_BN is not None or (x.shape[2] & 1) or (x.shape[3] & 3)):
-        dy = avgpool2_bwd(dy, x.shape[2], x.shape[3])  # (shapes / modes the fused read does not cover)
-        dy_pooled = False
-    _require(dy, y, x, mean, invstd, gamma, beta)
-    B, C = x.shape[0], x.shape[1]
-    HW = x.numel() // (B * C)
-    L = _lib.load()
-    ws = workspace(L.sivae_bn_workspace_bytes(B, C, HW), x.device)
-    dx = torch.empty_like(x)
-    dz = torch.empty_like(x) if want_dz else None
-    dgamma, dbeta = _pg(pg_out, C, x.device, want_param_grads)
-    if _bn_bwd_fused_ok(x, nseg):
-        _bn_bwd_fused(dy, y, None, x, mean, invstd, gamma, beta, act_mode, slope, dx, dz, dgamma, dbeta, dy_pooled, False,
-                      nseg)
-        return dx, dz, dgamma, dbeta
-    if nseg > 1 or (BN_FUSED_FINALIZE and SYNC_BN is None and x.dim() == 4):
-        _bn_bwd_seg(dy, y, None, x, mean, invstd, gamma, beta, act_mode, slope, dx, dz, dgamma, dbeta, dy_pooled, False,
-                    nseg)
-        return dx, dz, dgamma, dbeta
-    if SYNC_BN is not None:
-        local = torch.empty((C, 2), dtype=torch.float64, device=x.device)
-        _lib.call("sivae_bn_bwd_reduce", _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta),
-                  int(act_mode), float(slope), _p(local), B, C, HW, _p(ws), ws.numel(), _s())
-        glob = local.clone()
-        world = SYNC_BN(glob)
-        _lib.call("sivae_bn_bwd_apply", _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta),
-                  int(act_mode), float(slope), _p(local), _p(glob), float(B) * HW * world, _p(dx), _p(dz),
-                  _p(dgamma), _p(dbeta), B, C, HW, _p(ws), ws.numel(), _s())
-        return dx, dz, dgamma, dbeta
-    if dy_pooled:
-        _lib.call("sivae_bn_bwd_pooled_dy", _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta),
-                  int(act_mode), float(slope), _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, x.shape[2], x.shape[3],
-                  _p(ws), ws.numel(), _s())
-        return dx, dz, dgamma, dbeta
-    _lib.call("sivae_bn_bwd", _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode),
-              float(slope), _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, HW, _p(ws), ws.numel(), _s())
-    return dx, dz, dgamma, dbeta
+    return _bn_bwd_run("bn_bwd", dy, y, None, x, mean, invstd, gamma, beta, act_mode, slope, want_dz, False, dy_pooled,
+                       want_param_grads, pg_out, nseg)
 
 
 def channel_sum(x, out=None):
@@ -1353,3 +1323,15 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999
     bc2 = 1.0 - beta2 ** step
     _lib.call("sivae_adam_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), float(lr / bc1),
               float(beta1), float(beta2), float(eps), float(bc2 ** 0.5), float(grad_scale), _s())
+
+
+class _SwitchWatch(type(sys)):
+    """this module's type: assigning any of its attributes (ops.WINO4 = False, monkeypatch.setattr(ops, ...), dp's
+    ops.SYNC_BN = sync) forgets the memoised routes"""
+
+    def __setattr__(self, name, value):
+        super().__setattr__(name, value)
+        _routes.clear()
+
+
+sys.modules[__name__].__class__ = _SwitchWatch

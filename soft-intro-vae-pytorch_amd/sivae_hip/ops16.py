@@ -133,25 +133,19 @@ def conv2d(x, wp, Ci, Co, ks, bias=None, pro=None, upsample=False, want_stats=Fa
         rows = (L.sivae_bf16_conv2d_splitk_stats_rows(B, Ci, Co, H, W, ks) if splitk
                 else L.sivae_bf16_conv2d_num_px_tiles(B, Co, H, W, ks))
         stats = torch.empty((rows, Co, 2), dtype=torch.float32, device=x.device)
-    pm = pi = pg = pb = None
-    slope = 1.0
-    if pro is not None:
-        pm, pi, pg, pb, slope = pro
-        ops._require(pm, pi, pg, pb)
+    pm, pi, pg, pb, slope = ops._prologue(pro)
     ops._require(bias)
-    t0 = ops.TIMER.begin() if ops.TIMER is not None else None
+    t0 = ops.timer_begin()
     if splitk:
         ws = ops.workspace(L.sivae_bf16_conv2d_splitk_workspace_bytes(B, Ci, Co, H, W, ks), x.device)
-        _lib.call("sivae_bf16_conv2d_fwd_splitk", _p(x), _p(wp.data), _p(y), _p(pm), _p(pi), _p(pg), _p(pb),
-                  float(slope), _p(stats), B, Ci, Co, H, W, ks, int(bool(upsample)), int(bool(accumulate)), _p(ws),
-                  ws.numel(), _s(x))
+        _lib.call("sivae_bf16_conv2d_fwd_splitk", _p(x), _p(wp.data), _p(y), pm, pi, pg, pb, slope, _p(stats), B, Ci,
+                  Co, H, W, ks, int(bool(upsample)), int(bool(accumulate)), _p(ws), ws.numel(), _s(x))
     else:
-        _lib.call("sivae_bf16_conv2d_fwd", _p(x), _p(wp.data), _p(y), _p(bias), _p(pm), _p(pi), _p(pg), _p(pb),
-                  float(slope), _p(stats), B, Ci, Co, H, W, ks, int(bool(upsample)), int(bool(accumulate)),
-                  int(bool(out_f32)), _s(x))
+        _lib.call("sivae_bf16_conv2d_fwd", _p(x), _p(wp.data), _p(y), _p(bias), pm, pi, pg, pb, slope, _p(stats), B,
+                  Ci, Co, H, W, ks, int(bool(upsample)), int(bool(accumulate)), int(bool(out_f32)), _s(x))
     if t0 is not None:
-        ops.TIMER.end("bf16_conv_kernel<%d,%s>" % (ks, "co32" if Co <= 32 else ("co64" if Co <= 64 else "co128")),
-                      2.0 * B * H * W * Co * Ci * _taps(ks), t0)
+        ops.timer_end(t0, "bf16_conv_kernel<%d,%s>" % (ks, "co32" if Co <= 32 else ("co64" if Co <= 64 else "co128")),
+                      2.0 * B * H * W * Co * Ci * _taps(ks))
     return (y, stats) if want_stats else y
 
 
@@ -171,11 +165,11 @@ def conv2d_pool(x, wp, Ci, Co, out=None, accumulate=False):
     assert Cib == cblocks(Ci), (Cib, Ci)
     y = out if out is not None else empty_blocked(B, Co, H // 2, W // 2, x.device)
     assert tuple(y.shape) == (B, cblocks(Co), H // 2, W // 2, 8)
-    t0 = ops.TIMER.begin() if ops.TIMER is not None else None
+    t0 = ops.timer_begin()
     _lib.call("sivae_bf16_conv2d_fwd_pool", _p(x), _p(wp.data), _p(y), B, Ci, Co, H, W, int(bool(accumulate)), _s(x))
     if t0 is not None:
-        ops.TIMER.end("bf16_conv_kernel<3,%s>" % ("co32" if Co <= 32 else ("co64" if Co <= 64 else "co128")),
-                      2.0 * B * H * W * Co * Ci * 9, t0)
+        ops.timer_end(t0, "bf16_conv_kernel<3,%s>" % ("co32" if Co <= 32 else ("co64" if Co <= 64 else "co128")),
+                      2.0 * B * H * W * Co * Ci * 9)
     return y
 
 
@@ -187,16 +181,12 @@ def conv2d_wgrad(x, dy, Ci, Co, ks, pro=None, upsample=False, out=None):
     L = _lib.load()
     ws = ops.workspace(L.sivae_bf16_conv2d_wgrad_workspace_bytes(B, Ci, Co, H, W, ks), x.device)
     dw = ops._out(out, (Co, Ci, 5, 1) if ks == KS51 else (Co, Ci, ks, ks), x.device)
-    pm = pi = pg = pb = None
-    slope = 1.0
-    if pro is not None:
-        pm, pi, pg, pb, slope = pro
-        ops._require(pm, pi, pg, pb)
-    t0 = ops.TIMER.begin() if ops.TIMER is not None else None
-    _lib.call("sivae_bf16_conv2d_wgrad", _p(x), _p(dy), _p(dw), _p(pm), _p(pi), _p(pg), _p(pb), float(slope), B, Ci,
-              Co, H, W, ks, int(bool(upsample)), _p(ws), ws.numel(), _s(x))
+    pm, pi, pg, pb, slope = ops._prologue(pro)
+    t0 = ops.timer_begin()
+    _lib.call("sivae_bf16_conv2d_wgrad", _p(x), _p(dy), _p(dw), pm, pi, pg, pb, slope, B, Ci, Co, H, W, ks,
+              int(bool(upsample)), _p(ws), ws.numel(), _s(x))
     if t0 is not None:
-        ops.TIMER.end("bf16_wgrad_kernel<%d>" % ks, 2.0 * B * H * W * Co * Ci * _taps(ks), t0)
+        ops.timer_end(t0, "bf16_wgrad_kernel<%d>" % ks, 2.0 * B * H * W * Co * Ci * _taps(ks))
     return dw
 
 

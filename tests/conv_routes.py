@@ -1,0 +1,508 @@
+"""Characterisation of the fp32 dispatch of sivae_hip.ops, recorded without a GPU.
+
+The public launch functions (conv2d_fwd, conv2d_wgrad, conv2d_up_dgrad, conv2d_dgrad_bnbwd, bn_bwd, bn_bwd_signmask,
+bn_bwd_dzsum) are driven with device="meta" tensors while the helpers every launch goes through are replaced:
+`ops._lib.call` by a recorder, `ops._require` by a no-op, `ops._p` by "null / non-null", `ops._s` by a constant,
+`ops.workspace` / `ops.counters` / `ops.bn_fused_state` by meta-tensor allocators, `ops.TIMER` by a fake timer.  Only
+library predicates run (they need no device: without one sivae_num_cus() answers 256, the MI355X's count).
+
+A case's record is, in order: every C entry point called with its scalar arguments and the null ("-") / non-null ("p")
+pattern of its pointer arguments, the timer key with `flops` and `executed`, and the shapes of the returned tensors —
+or, for a combination the code refuses, the exception type and message (sivae_pack_* calls made before a refusal are
+dropped: packing a weight before refusing the call is not behaviour anyone relies on).
+
+The module patches only names that are part of the package's surface, so the same file records any commit:
+
+    python tests/conv_routes.py            # writes tests/golden/conv_routes_fp32.json.gz
+
+tests/test_conv_routes_host.py replays it in-process and compares with the committed fixture.
+"""
+import contextlib
+import gzip
+import json
+import os
+import sys
+
+import torch
+
+for _d in (os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "soft-intro-vae-pytorch_amd"),):
+    _d = os.path.abspath(_d)
+    if _d not in sys.path:
+        sys.path.insert(0, _d)
+
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_routes_fp32.json.gz")
+
+# every switch of the dispatch, set explicitly (the recording must not depend on SIVAE_* variables of the environment)
+SWITCHES = dict(WINO=True, WINO_UP=True, WINO4=True, WINO4_B6=False, WINO4_B6_MINC=16, WINO4_B6_PRO=True,
+                WINO4_MAXC=512, WINO4_WGRAD=True, WINO4_FORCE=False, WINO4_SPLITK=True, WINO4_SMALL=True,
+                WINO4_SMALL_FORCE=False, WINO4_UP_SMALL=True, WINO4_DGRAD_POOL=True, WINO4_PRO=True,
+                FUSE_BN_BWD=False, WINO_WGRAD=True, CONV1_STREAM=True, CONV5_K75=True, SIGNMASK=True, BN_FUSED=True,
+                BN_FUSED_FINALIZE=False, SYNC_BN=None)
+
+
+def _sync_stub(sums):
+    return 2  # (world size; the sums stay as they are)
+
+
+# (name, switch overrides, SIVAE_DP_SAME_DEVICE): "default" records the full case table, the others a thinned one
+VARIANTS = [("default", {}, "0"), ("WINO=0", dict(WINO=False), "0"),
+            ("WINO4=0", dict(WINO4=False, WINO4_WGRAD=False), "0"), ("WINO4_FORCE=1", dict(WINO4_FORCE=True), "0"),
+            ("WINO4_SMALL=0", dict(WINO4_SMALL=False), "0"), ("WINO4_SMALL_FORCE=1", dict(WINO4_SMALL_FORCE=True), "0"),
+            ("WINO4_UP_SMALL=0", dict(WINO4_UP_SMALL=False), "0"), ("WINO4_SPLITK=0", dict(WINO4_SPLITK=False), "0"),
+            ("WINO4_PRO=0", dict(WINO4_PRO=False), "0"), ("WINO4_DGRAD_POOL=0", dict(WINO4_DGRAD_POOL=False), "0"),
+            ("WINO4_B6=1", dict(WINO4_B6=True), "0"), ("WINO_UP=0", dict(WINO_UP=False), "0"),
+            ("WINO_WGRAD=0", dict(WINO_WGRAD=False), "0"), ("CONV1_STREAM=0", dict(CONV1_STREAM=False), "0"),
+            ("CONV5_K75=0", dict(CONV5_K75=False), "0"), ("FUSE_BN_BWD=1", dict(FUSE_BN_BWD=True), "0"),
+            ("BN_FUSED=0", dict(BN_FUSED=False), "0"), ("BN_FUSED_FINALIZE=1", dict(BN_FUSED_FINALIZE=True), "0"),
+            ("SIVAE_DP_SAME_DEVICE=1", {}, "1"), ("SYNC_BN", dict(SYNC_BN=_sync_stub), "0")]
+
+
+# ---- recorder --------------------------------------------------------------------------------------------------------
+class _Ptr:
+    pass
+
+
+_PTR, _STREAM = _Ptr(), _Ptr()
+
+
+def _enc(a):
+    if a is None:
+        return "-"
+    if a is _PTR:
+        return "p"
+    if a is _STREAM:
+        return "s"
+    if isinstance(a, bool):
+        return int(a)
+    if isinstance(a, (int, float)):
+        return a
+    raise TypeError("conv_routes: unexpected argument %r in a C-ABI call" % (a,))
+
+
+class _FakeTimer:
+    def __init__(self, events):
+        self.events = events
+
+    def begin(self):
+        return self
+
+    def end(self, key, flops, start, executed=None):
+        assert start is self
+        self.events.append(["timer", key, flops, flops if executed is None else executed])
+
+
+class _Mask:
+    """stands for the uint8 device sign mask bn_apply_act_signmask returns (a meta tensor is not `is_cuda`)"""
+    dtype = torch.uint8
+    is_cuda = True
+
+    def numel(self):
+        return 1 << 40
+
+
+def M(*shape, dtype=torch.float32):
+    return torch.empty(shape, dtype=dtype, device="meta")
+
+
+@contextlib.contextmanager
+def recording(switches=None, same_device="0"):
+    """patch sivae_hip.ops as the module docstring says; yields (ops, events) — `events` is the list the recorder
+    appends to (clear it between cases)"""
+    from sivae_hip import ops
+    events = []
+    names = list(SWITCHES) + ["_require", "_p", "_s", "workspace", "counters", "bn_fused_state", "TIMER"]
+    saved = {n: getattr(ops, n) for n in names}
+    saved_call = ops._lib.call
+    saved_env = os.environ.get("SIVAE_DP_SAME_DEVICE")
+    try:
+        for n, v in dict(SWITCHES, **(switches or {})).items():
+            setattr(ops, n, v)
+        os.environ["SIVAE_DP_SAME_DEVICE"] = same_device
+        ops._require = lambda *tensors: None
+        ops._p = lambda t: None if t is None else _PTR
+        ops._s = lambda t=None: _STREAM
+        ops.workspace = lambda nbytes, device: torch.empty(int(nbytes), dtype=torch.uint8, device="meta")
+        ops.counters = lambda device: torch.empty(8192, dtype=torch.int32, device="meta")
+        ops.bn_fused_state = lambda device: torch.empty(64, dtype=torch.int32, device="meta")
+        ops.TIMER = _FakeTimer(events)
+        ops._lib.call = lambda name, *args: events.append(["call", name] + [_enc(a) for a in args])
+        yield ops, events
+    finally:
+        ops._lib.call = saved_call
+        for n, v in saved.items():
+            setattr(ops, n, v)
+        if saved_env is None:
+            os.environ.pop("SIVAE_DP_SAME_DEVICE", None)
+        else:
+            os.environ["SIVAE_DP_SAME_DEVICE"] = saved_env
+
+
+# ---- runners: one public call per case -------------------------------------------------------------------------------
+def _pro(C, nseg):
+    return (M(nseg * C), M(nseg * C), M(C), M(C), 0.2)
+
+
+def run_fwd(ops, B, Ci, Co, H, W, ks, packed=True, mode=0, bias=False, pro=False, upsample=False, want_stats=False,
+            has_out=False, accumulate=False, nseg=1):
+    x = M(B, Ci, H // 2, W // 2) if upsample else M(B, Ci, H, W)
+    w = M(Co, Ci, ks, ks) if mode == 0 else M(Ci, Co, ks, ks)
+    wp = ops.PackedW(w, mode) if packed else ops.pack_weight(w, mode)
+    return ops.conv2d_fwd(x, wp, Co, ks, bias=M(Co) if bias else None, pro=_pro(Ci, nseg) if pro else None,
+                          upsample=upsample, want_stats=want_stats, out=M(B, Co, H, W) if has_out else None,
+                          accumulate=accumulate, nseg=nseg)
+
+
+def run_wgrad(ops, B, Ci, Co, H, W, ks, pro=False, upsample=False, has_out=False, nseg=1):
+    x = M(B, Ci, H // 2, W // 2) if upsample else M(B, Ci, H, W)
+    return ops.conv2d_wgrad(x, M(B, Co, H, W), ks, pro=_pro(Ci, nseg) if pro else None, upsample=upsample,
+                            out=M(Co, Ci, ks, ks) if has_out else None, nseg=nseg)
+
+
+def run_up_dgrad(ops, B, C, N, H, W, has_wp1=False, has_out=False, accumulate=False):
+    w = M(C, N, 3, 3)
+    return ops.conv2d_up_dgrad(M(B, C, H, W), ops.PackedW(w, 0), N, out=M(B, N, H // 2, W // 2) if has_out else None,
+                               accumulate=accumulate, wp1=ops.PackedW(w, 1) if has_wp1 else None)
+
+
+def run_dgrad_bnbwd(ops, B, Ci, Cm, H, W):
+    return ops.conv2d_dgrad_bnbwd(M(B, Ci, H, W), ops.PackedW(M(Ci, Cm, 3, 3), 1), Cm, M(B, Cm, H, W), M(Cm), M(Cm),
+                                  M(Cm), M(Cm))
+
+
+def run_bn_bwd(ops, B, C, H, W, act=1, want_dz=False, dy_pooled=False, has_pg_out=False, nseg=1, flat=False):
+    x = M(B, C) if flat else M(B, C, H, W)
+    dy = M(B, C, H // 2, W // 2) if dy_pooled else torch.empty_like(x)
+    return ops.bn_bwd(dy, torch.empty_like(x) if act == 1 else None, x, M(nseg * C), M(nseg * C), M(C),
+                      want_dz=want_dz, beta=M(C) if act == 2 else None, act_mode=act, dy_pooled=dy_pooled,
+                      pg_out=(M(C), M(C)) if has_pg_out else None, nseg=nseg)
+
+
+def run_bn_signmask(ops, B, C, H, W, dy_pooled=False, dz_sum=False, want_dz=True, nseg=1):
+    x = M(B, C, H, W)
+    dy = M(B, C, H // 2, W // 2) if dy_pooled else torch.empty_like(x)
+    return ops.bn_bwd_signmask(dy, _Mask(), x, M(nseg * C), M(nseg * C), M(C), dy_pooled=dy_pooled, dz_sum=dz_sum,
+                               want_dz=want_dz, nseg=nseg)
+
+
+def run_bn_dzsum(ops, B, C, H, W, nseg=1):
+    x = M(B, C, H, W)
+    return ops.bn_bwd_dzsum(torch.empty_like(x), torch.empty_like(x), x, M(nseg * C), M(nseg * C), M(C), nseg=nseg)
+
+
+RUNNERS = dict(fwd=run_fwd, wgrad=run_wgrad, up_dgrad=run_up_dgrad, dgrad_bnbwd=run_dgrad_bnbwd, bn_bwd=run_bn_bwd,
+               bn_signmask=run_bn_signmask, bn_dzsum=run_bn_dzsum)
+
+
+def _shapes(r):
+    if r is None:
+        return None
+    if isinstance(r, (tuple, list)):
+        return [_shapes(t) for t in r]
+    return list(r.shape)
+
+
+def record_case(ops, events, kind, params):
+    del events[:]
+    try:
+        ret = RUNNERS[kind](ops, **params)
+    except Exception as e:  # noqa: BLE001  (a refusal is part of the behaviour recorded)
+        return [ev for ev in events if not (ev[0] == "call" and ev[1].startswith("sivae_pack_"))] + [
+            ["raise", type(e).__name__, str(e)]]
+    return list(events) + [["ret", _shapes(ret)]]
+
+
+def case_name(kind, params):
+    return kind + " " + " ".join("%s=%s" % (k, int(v) if isinstance(v, bool) else v) for k, v in params.items())
+
+
+# ---- case table ------------------------------------------------------------------------------------------------------
+MAPS = (4, 8, 16, 32, 64, 128, 256)
+CH = (16, 32, 64, 128, 256, 512)
+
+
+def _skip(S, *chans):
+    return S >= 128 and max(chans) > 128
+
+
+def table_cases(thin):
+    """[(kind, params)] of the generated table; thin: the smaller table of the switch variants"""
+    out = []
+    batches = (128, 16) if thin else (128, 64, 16, 8, 2, 3)
+    if thin:
+        pairs = [(16, 16), (64, 64), (512, 512), (128, 64), (64, 128)]
+    else:
+        pairs = [(c, c) for c in CH] + [(c, 2 * c) for c in CH[:-1]] + [(2 * c, c) for c in CH[:-1]]
+    # 3x3 layers
+    fwd_flags = [{}, dict(mode=1), dict(pro=True), dict(want_stats=True), dict(pro=True, want_stats=True),
+                 dict(upsample=True), dict(upsample=True, want_stats=True), dict(upsample=True, pro=True),
+                 dict(mode=1, has_out=True, accumulate=True), dict(upsample=True, has_out=True, accumulate=True),
+                 dict(has_out=True), dict(packed=False), dict(packed=False, pro=True, want_stats=True),
+                 dict(bias=True), dict(nseg=2, want_stats=True), dict(nseg=2, pro=True, want_stats=True),
+                 dict(nseg=2, pro=True), dict(nseg=2, upsample=True, want_stats=True), dict(nseg=2, mode=1),
+                 dict(nseg=2, upsample=True, pro=True, want_stats=True), dict(nseg=2, packed=False, want_stats=True)]
+    wg_flags = [{}, dict(pro=True), dict(upsample=True), dict(upsample=True, pro=True), dict(has_out=True),
+                dict(nseg=2), dict(nseg=2, pro=True), dict(nseg=2, pro=True, has_out=True),
+                dict(nseg=2, upsample=True)]
+    for B in batches:
+        for S in MAPS:
+            for Ci, Co in pairs:
+                if _skip(S, Ci, Co):
+                    continue
+                for fl in fwd_flags:
+                    if fl.get("nseg", 1) > 1 and B % 2:
+                        continue
+                    out.append(("fwd", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=3, **fl)))
+                for fl in wg_flags:
+                    if fl.get("nseg", 1) > 1 and B % 2:
+                        continue
+                    out.append(("wgrad", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=3, **fl)))
+    # non-square and odd maps the Winograd kernels refuse or tile differently
+    for B in (128, 2):
+        for H, W in ((8, 16), (16, 8), (6, 6), (7, 7), (32, 24), (12, 20)):
+            for fl in ({}, dict(pro=True, want_stats=True), dict(upsample=True), dict(nseg=2, pro=True, want_stats=True)):
+                out.append(("fwd", dict(B=B, Ci=64, Co=64, H=H, W=W, ks=3, **fl)))
+            for fl in ({}, dict(pro=True), dict(upsample=True), dict(nseg=2, pro=True)):
+                out.append(("wgrad", dict(B=B, Ci=64, Co=64, H=H, W=W, ks=3, **fl)))
+    # 1x1 layers (ResidualBlock.conv_expand; H = W = 1: the Linear layers the small-batch GEMM does not take)
+    for B in batches:
+        for S in (1,) + MAPS[:-1]:
+            for Ci, Co in pairs:
+                if _skip(S, Ci, Co):
+                    continue
+                for fl in ({}, dict(mode=1), dict(bias=True), dict(mode=1, has_out=True, accumulate=True),
+                           dict(packed=False), dict(want_stats=True), dict(pro=True)):
+                    out.append(("fwd", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=1, **fl)))
+                for fl in ({}, dict(has_out=True)):
+                    out.append(("wgrad", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=1, **fl)))
+    # 5x5 layers with 1 / 3 / 4 image channels on either side (encoder stem, Decoder.predict)
+    for B in batches:
+        for S in (32, 128, 256):
+            for small in (1, 3, 4):
+                for big in (16, 64, 128):
+                    for Ci, Co in ((small, big), (big, small)):
+                        for fl in ({}, dict(want_stats=True), dict(bias=True), dict(mode=1), dict(packed=False),
+                                   dict(has_out=True), dict(nseg=2, want_stats=True)):
+                            out.append(("fwd", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=5, **fl)))
+                        out.append(("wgrad", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=5)))
+    # data gradient of conv3x3(Upsample2(x)) to the low-resolution x; conv2's data gradient with BatchNorm-1's sums
+    for B in batches:
+        for S in MAPS[1:]:
+            for C, N in pairs:
+                if _skip(S, C, N):
+                    continue
+                for fl in ({}, dict(has_wp1=True), dict(has_wp1=True, has_out=True, accumulate=True),
+                           dict(has_out=True, accumulate=True)):
+                    out.append(("up_dgrad", dict(B=B, C=C, N=N, H=S, W=S, **fl)))
+                out.append(("dgrad_bnbwd", dict(B=B, Ci=C, Cm=N, H=S, W=S)))
+    # the three BatchNorm backwards
+    for B in batches:
+        for S in MAPS + (6,):
+            for C in (16, 64, 512):
+                if _skip(S, C):
+                    continue
+                for nseg in (1, 2):
+                    if B % nseg:
+                        continue
+                    for fl in (dict(act=1, want_dz=True), dict(act=1, want_dz=True, dy_pooled=True), dict(act=1),
+                               dict(act=2), dict(act=2, dy_pooled=True), dict(act=0), dict(act=2, has_pg_out=True)):
+                        out.append(("bn_bwd", dict(B=B, C=C, H=S, W=S, nseg=nseg, **fl)))
+                    for fl in ({}, dict(dy_pooled=True), dict(dz_sum=True), dict(want_dz=False)):
+                        out.append(("bn_signmask", dict(B=B, C=C, H=S, W=S, nseg=nseg, **fl)))
+                    out.append(("bn_dzsum", dict(B=B, C=C, H=S, W=S, nseg=nseg)))
+        out.append(("bn_bwd", dict(B=B, C=512, H=1, W=1, act=0, flat=True)))
+    return out
+
+
+# ---- the benchmarked networks ----------------------------------------------------------------------------------------
+# (bench.py: celeb256 at batch 128 and as a 16-image shard, the bootstrap variant at 256x256 with 64 and 8 images,
+# cifar10 at batch 256; each unpaired and as segmented pairs)
+NETWORKS = [("celeb256_bs128", [64, 128, 256, 512, 512, 512], 256, 128),
+            ("celeb256_bs16", [64, 128, 256, 512, 512, 512], 256, 16),
+            ("bootstrap256_bs64", [64, 128, 256, 512, 512, 512], 256, 64),
+            ("bootstrap256_bs8", [64, 128, 256, 512, 512, 512], 256, 8),
+            ("cifar10_bs256", [64, 128, 256], 32, 256)]
+
+
+def block_cases(ops, B, Ci, Cm, Co, H, W, x_up, post, nseg, has_exp):
+    """the ops-level calls of one training-mode functional.ResBlockFn forward + backward (every gradient needed,
+    parameter gradients written into slabs), in its order; H, W: the block's resolution"""
+    out = []
+
+    def add(kind, **p):
+        out.append((kind, p))
+
+    Hs, Ws = (H // 2, W // 2) if x_up else (H, W)
+    if has_exp:
+        add("fwd", B=B, Ci=Ci, Co=Co, H=Hs, W=Ws, ks=1)
+    add("fwd", B=B, Ci=Ci, Co=Cm, H=H, W=W, ks=3, want_stats=True, upsample=x_up, nseg=nseg)
+    h_saved = nseg > 1 and not ops.seg_prologue_supported(H, W)
+    add("fwd", B=B, Ci=Cm, Co=Co, H=H, W=W, ks=3, pro=not h_saved, want_stats=True, nseg=nseg)
+    c = M(B, Co, H, W)
+    pooled = post == "pool" and not (x_up and not has_exp)
+    dzh = False
+    if ops.bn_signmask_supported(c):
+        dzh = (not pooled) and x_up and post != "pool"
+        add("bn_signmask", B=B, C=Co, H=H, W=W, dy_pooled=pooled, dz_sum=dzh, nseg=nseg)
+    elif x_up and post != "pool" and ops.bn_bwd_dzsum_supported(c):
+        dzh = True
+        add("bn_dzsum", B=B, C=Co, H=H, W=W, nseg=nseg)
+    else:
+        add("bn_bwd", B=B, C=Co, H=H, W=W, act=1, want_dz=True, dy_pooled=post == "pool", has_pg_out=True, nseg=nseg)
+    add("wgrad", B=B, Ci=Cm, Co=Co, H=H, W=W, ks=3, pro=not h_saved, has_out=True, nseg=nseg)
+    if (not h_saved) and nseg == 1 and ops.conv2d_dgrad_bnbwd_supported(H, W):
+        add("dgrad_bnbwd", B=B, Ci=Co, Cm=Cm, H=H, W=W)
+    else:
+        add("fwd", B=B, Ci=Co, Co=Cm, H=H, W=W, ks=3, mode=1)
+        add("bn_bwd", B=B, C=Cm, H=H, W=W, act=1 if h_saved else 2, has_pg_out=True, nseg=nseg)
+    add("wgrad", B=B, Ci=Ci, Co=Cm, H=H, W=W, ks=3, upsample=x_up, has_out=True)
+    up_dg = x_up and ops.conv2d_up_dgrad_supported(Hs, Ws)
+    if has_exp and x_up:
+        add("wgrad", B=B, Ci=Ci, Co=Co, H=Hs, W=Ws, ks=1, has_out=True)
+        if up_dg:
+            add("up_dgrad", B=B, C=Cm, N=Ci, H=H, W=W, has_wp1=True)
+        else:
+            add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1)
+        add("fwd", B=B, Ci=Co, Co=Ci, H=Hs, W=Ws, ks=1, mode=1, has_out=True, accumulate=True)
+    elif up_dg:
+        add("up_dgrad", B=B, C=Cm, N=Ci, H=H, W=W, has_wp1=True, has_out=True, accumulate=True)
+    elif x_up and dzh:
+        add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1)
+    elif has_exp:
+        add("wgrad", B=B, Ci=Ci, Co=Co, H=H, W=W, ks=1, has_out=True)
+        add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1)
+        add("fwd", B=B, Ci=Co, Co=Ci, H=H, W=W, ks=1, mode=1, has_out=True, accumulate=True)
+    else:
+        add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1, has_out=True, accumulate=True)
+    return out
+
+
+def network_cases(ops, channels, image_size, B, nseg=1, cdim=3):
+    """[(layer, kind, params)]: nn._run_main walked over the fp32 Encoder and Decoder on meta tensors with the block /
+    stem / predict entry points replaced by functions that list the ops-level calls they would make (nothing runs)"""
+    from sivae_hip import functional as SF
+    from sivae_hip import nn as N
+    out = []
+    where = [""]
+
+    def blk(self, x, post=None, cache=None, x_up=False, nseg=1, seg_rev=False, replay_update=True):
+        Bx, Ci, H, W = x.shape
+        if x_up:
+            H, W = 2 * H, 2 * W
+        Cm, Co = self.conv1.out_channels, self.conv2.out_channels
+        layer = "%s.block%dx%d" % (where[0], H, W)
+        out.extend((layer, k, p) for k, p in block_cases(ops, Bx, Ci, Cm, Co, H, W, x_up, post, nseg,
+                                                         self.conv_expand is not None))
+        Ho, Wo = (H // 2, W // 2) if post == "pool" else ((2 * H, 2 * W) if post == "up" else (H, W))
+        return M(Bx, Co, Ho, Wo)
+
+    def stem(x, w, g, b, st, nseg=1, seg_rev=False):
+        Bx, Ci, H, W = x.shape
+        Co = w.shape[0]
+        out.append((where[0] + ".stem", "fwd", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=5, want_stats=True)))
+        out.append((where[0] + ".stem", "bn_bwd", dict(B=Bx, C=Co, H=H, W=W, act=2, dy_pooled=True, has_pg_out=True,
+                                                       nseg=nseg)))
+        if not (SF._is_edge5(w) and Ci <= 3):
+            out.append((where[0] + ".stem", "wgrad", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=5, has_out=True)))
+        return M(Bx, Co, H // 2, W // 2)
+
+    def conv_bias(x, w, bias, cache=None):
+        Bx, Ci, H, W = x.shape
+        Co, ks = w.shape[0], w.shape[2]
+        if not (SF._is_edge5(w) and Co <= 3):
+            out.append((where[0] + ".predict", "fwd", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=ks, bias=bias is not None)))
+        if not SF._is_edge5(w):
+            out.append((where[0] + ".predict", "wgrad", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=ks, has_out=True)))
+        out.append((where[0] + ".predict", "fwd", dict(B=Bx, Ci=Co, Co=Ci, H=H, W=W, ks=ks, mode=1)))
+        return M(Bx, Co, H, W)
+
+    orig = (N.ResidualBlock.forward, SF.stem, SF.conv_bias)
+    try:
+        N.ResidualBlock.forward, SF.stem, SF.conv_bias = blk, stem, conv_bias
+        with torch.device("meta"), contextlib.redirect_stdout(None):  # (the constructors print their shapes)
+            enc = N.Encoder(cdim, 8, channels, image_size)
+            dec = N.Decoder(cdim, 8, channels, image_size, conv_input_size=enc.conv_output_size)
+        where[0] = "enc"
+        N._run_main(enc.main, M(B, cdim, image_size, image_size), nseg=nseg)
+        where[0] = "dec"
+        N._run_main(dec.main, M(B, *enc.conv_output_size), nseg=nseg)
+    finally:
+        N.ResidualBlock.forward, SF.stem, SF.conv_bias = orig
+    return out
+
+
+# ---- recording -------------------------------------------------------------------------------------------------------
+def variant_cases(ops, vname):
+    """[(case name, kind, params)] of one switch variant (call inside `recording` of that variant: the network walk asks
+    the ops module which block forms the switches allow)"""
+    seen, out = set(), []
+    for kind, p in table_cases(thin=vname != "default"):
+        name = case_name(kind, p)
+        if name not in seen:
+            seen.add(name)
+            out.append((name, kind, p))
+    if vname == "default":
+        for net, channels, size, B in NETWORKS:
+            for nseg in (1, 2):
+                for layer, kind, p in network_cases(ops, channels, size, B * nseg, nseg):
+                    out.append(("%s nseg=%d %s: %s" % (net, nseg, layer, case_name(kind, p)), kind, p))
+    return out
+
+
+def generate(on_case=None):
+    """-> {variant: [(case name, record)]}; on_case(ops, variant, name, kind, params, record) is called for every case
+    while the variant's switches are still set"""
+    out = {}
+    for vname, switches, same_device in VARIANTS:
+        with recording(switches, same_device) as (ops, events):
+            rows = []
+            for name, kind, p in variant_cases(ops, vname):
+                rec = record_case(ops, events, kind, p)
+                rows.append((name, rec))
+                if on_case is not None:
+                    on_case(ops, vname, name, kind, p, rec)
+            out[vname] = rows
+    return out
+
+
+def compact(gen):
+    """{"records": [unique records], "names": [unique case-name lists], "variants": {variant: [index into names,
+    [record index of each case]]}}"""
+    index, records, nindex, names, variants = {}, [], {}, [], {}
+    for vname, rows in gen.items():
+        vr = []
+        for _, rec in rows:
+            key = json.dumps(rec)
+            if key not in index:
+                index[key] = len(records)
+                records.append(rec)
+            vr.append(index[key])
+        nkey = tuple(name for name, _ in rows)
+        if nkey not in nindex:
+            nindex[nkey] = len(names)
+            names.append(list(nkey))
+        variants[vname] = [nindex[nkey], vr]
+    return dict(records=records, names=names, variants=variants)
+
+
+def expand(fixture):
+    """the inverse of `compact`: {variant: [(case name, record)]}"""
+    return {v: [(name, fixture["records"][i]) for name, i in zip(fixture["names"][ni], idx)]
+            for v, (ni, idx) in fixture["variants"].items()}
+
+
+def load_fixture(path=FIXTURE):
+    with gzip.open(path, "rt", encoding="utf-8") as f:
+        return json.load(f)
+
+
+def write_fixture(path=FIXTURE):
+    data = json.dumps(compact(generate()), separators=(",", ":")).encode("utf-8")
+    with open(path, "wb") as raw:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0, compresslevel=9) as f:
+            f.write(data)
+    return len(data), os.path.getsize(path)
+
+
+if __name__ == "__main__":
+    n, z = write_fixture(sys.argv[1] if len(sys.argv) > 1 else FIXTURE)
+    print("wrote %s: %d bytes of JSON, %d compressed" % (sys.argv[1] if len(sys.argv) > 1 else FIXTURE, n, z))
