@@ -17,7 +17,9 @@ Frozen networks (requires_grad=False) still run BatchNorm in training mode and u
 statistics, as in the reference; weight gradients are skipped per `needs_input_grad` — this is what makes
 the iteration cost 13 F_E + 19 F_D.
 """
+import collections
 import os
+import sys
 
 import torch
 
@@ -52,9 +54,9 @@ def _wtag(w):
     return (w._version, getattr(w, "_sivae_gen", 0), w.data_ptr(), _epoch[0])
 
 
-def _cached_pack(w, slot, build):
+def _cached_pack(w, slot, build, attr="_sivae_pack"):
     """packs live ON the parameter object (they die with it; no id() aliasing, nothing accumulates across models)"""
-    store = w.__dict__.setdefault("_sivae_pack", {})
+    store = w.__dict__.setdefault(attr, {})
     tag = _wtag(w)
     hit = store.get(slot)
     if hit is not None and hit[0] == tag:
@@ -73,15 +75,55 @@ def packed(w, mode):
 PACK_BATCH = os.environ.get("SIVAE_PACK_BATCH", "1") != "0"
 
 
+def _pack_batch(owner, attr, jobs):
+    """Rebuild cached operand forms IN PLACE, one sivae_pack_batch launch per form.  jobs: {form: [(w, buf, mode)]} (w: the
+    detached alias of the parameter the form is built from, buf: the form's buffer).  The job tables live on `owner`
+    under `attr` and are rebuilt only when the set of cached forms changes (the first iterations).
+    -> False when nothing was launched: the forms stay invalid and are rebuilt one by one on their next use."""
+    import ctypes
+    L = ops._lib.load()
+    key = tuple((f, w.data_ptr(), buf.data_ptr(), mode) for f in sorted(jobs) for w, buf, mode in jobs[f])
+    plan = owner.__dict__.get(attr)
+    if plan is None or plan["key"] != key:
+        if torch.cuda.is_current_stream_capturing():
+            return False  # (building the job tables uploads them — not capturable)
+        if any(len(js) > 32767 for js in jobs.values()):
+            return False  # (the block -> job map is 16 bits wide)
+        jb = L.sivae_pack_job_bytes()
+        launches = []
+        for f in sorted(jobs):
+            host = ctypes.create_string_buffer(jb * len(jobs[f]))
+            block_job, nblocks = [], 0
+            for i, (w, buf, mode) in enumerate(jobs[f]):
+                nb = L.sivae_pack_job_fill(host, i, f, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(buf.data_ptr()),
+                                           w.shape[0], w.shape[1], w.shape[2] if w.dim() == 4 else 1, mode, nblocks)
+                if nb <= 0:
+                    raise ops._lib.SivaeError("sivae_pack_job_fill", nb)
+                block_job.extend([i] * nb)
+                nblocks += nb
+            dev = jobs[f][0][0].device
+            jt = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(dev)
+            bj = torch.tensor(block_job, dtype=torch.int16).to(dev)  # (indices < 32768: uint16 and int16 agree)
+            launches.append((f, jt, bj, nblocks))
+        # (job tables of earlier plans stay alive: a HIP graph captured while they were current still launches with them)
+        # — the last few only: a workload whose set of cached forms oscillates would otherwise accumulate device memory
+        if plan is not None:
+            old = owner.__dict__.setdefault(attr + "_old", [])
+            old.append(plan)
+            del old[:-4]
+        plan = {"key": key, "launches": launches, "keep": [buf for f in sorted(jobs) for _, buf, _ in jobs[f]]}
+        owner.__dict__[attr] = plan
+    for f, jt, bj, nblocks in plan["launches"]:
+        ops._lib.call("sivae_pack_batch", f, ops._p(jt), ops._p(bj), nblocks, ops._s(jt))
+    return True
+
+
 def repack(params, owner):
     """After `params` were updated in place through raw pointers (FlatAdam.step, generation already bumped): rebuild every
-    operand form cached on them IN PLACE with one launch per form (sivae_pack_batch) and re-validate the caches.  The job
-    tables live on `owner` and are rebuilt only when the set of cached forms changes (the first iterations)."""
-    import ctypes
+    operand form cached on them IN PLACE with one launch per form (`_pack_batch`) and re-validate the caches."""
     if not PACK_BATCH:
         return
-    L = ops._lib.load()
-    entries, jobs = [], [[] for _ in range(6)]
+    entries, jobs = [], {}
     for p in params:
         store = p.__dict__.get("_sivae_pack")
         if not store:
@@ -98,54 +140,13 @@ def repack(params, owner):
                 if forms:
                     entries.append((p, store, slot, obj))
                     for f, buf in forms:
-                        jobs[f].append((obj, buf))
+                        jobs.setdefault(f, []).append((obj.w, buf, obj.mode))
                 else:
                     del store[slot]
             else:
                 del store[slot]  # (the small-channel 5x5 packs: rebuilt on demand)
-    if not entries:
+    if not entries or not _pack_batch(owner, "_sivae_pack_plan", jobs):
         return
-    key = tuple((f, obj.w.data_ptr(), buf.data_ptr()) for f in range(6) for obj, buf in jobs[f])
-    plan = owner.__dict__.get("_sivae_pack_plan")
-    if plan is None or plan["key"] != key:
-        if torch.cuda.is_current_stream_capturing():
-            # (building the job tables uploads them — not capturable; the forms stay invalid and are rebuilt one by one on
-            # their next use, inside the capture, as before round 4)
-            return
-        jb = L.sivae_pack_job_bytes()
-        dev = entries[0][0].device
-        launches = []
-        for f in range(6):
-            if not jobs[f]:
-                continue
-            if len(jobs[f]) > 32767:
-                return  # (the block -> job map is 16 bits wide)
-            host = ctypes.create_string_buffer(jb * len(jobs[f]))
-            block_job, nblocks = [], 0
-            for i, (obj, buf) in enumerate(jobs[f]):
-                w = obj.w
-                Co, Ci = w.shape[0], w.shape[1]
-                ks = w.shape[2] if w.dim() == 4 else 1
-                nb = L.sivae_pack_job_fill(host, i, f, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(buf.data_ptr()),
-                                           Co, Ci, ks, obj.mode, nblocks)
-                if nb <= 0:
-                    raise ops._lib.SivaeError("sivae_pack_job_fill", nb)
-                block_job.extend([i] * nb)
-                nblocks += nb
-            jt = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(dev)
-            bj = torch.tensor(block_job, dtype=torch.int16).to(dev)  # (indices < 32768: uint16 and int16 agree)
-            launches.append((f, jt, bj, nblocks))
-        plan = {"key": key, "launches": launches, "keep": [b for fl in jobs for _, b in fl]}
-        # (job tables of earlier plans stay alive: a HIP graph captured while they were current still launches with them)
-        # — the last few only: a workload whose set of cached forms oscillates would otherwise accumulate device memory
-        prev = owner.__dict__.get("_sivae_pack_plan")
-        if prev is not None:
-            old = owner.__dict__.setdefault("_sivae_pack_plan_old", [])
-            old.append(prev)
-            del old[:-4]
-        owner.__dict__["_sivae_pack_plan"] = plan
-    for f, jt, bj, nblocks in plan["launches"]:
-        ops._lib.call("sivae_pack_batch", f, ops._p(jt), ops._p(bj), nblocks, ops._s(jt))
     for p, store, slot, obj in entries:
         obj.refreshed()
         store[slot] = (_wtag(p), obj)
@@ -284,15 +285,119 @@ def _done(*params):
             cb(p)
 
 
+def _hand(grad, p, k):
+    """a parameter gradient, once the kernel that wrote it has been enqueued: one that went into its slab (k >= 0) is
+    announced to the gradient synchroniser and NOT handed to autograd"""
+    if k < 0:
+        return grad
+    _done(p)
+    return None
+
+
+def _hand_bn(pg, g, b, dg, db, need_g, need_b):
+    """`_hand` for the (dgamma, dbeta) pair of a BatchNorm backward (pg: `_pg_dst`, both direct or neither)"""
+    if pg is not None:
+        _done(g, b)
+        return None, None
+    return dg if need_g else None, db if need_b else None
+
+
+def _replay(cache, tag, names, bn=(), count=0, nseg=1, seg_rev=False, replay_update=True):
+    """The replay-cache preamble of a block / predict forward: -> the cached tensors `names` of a pass that is still
+    valid (filled, and the same weights: `tag`), or None — run the kernels and fill the cache.  A replay runs no kernel
+    except the running-statistics updates the pass would have made (bn: (BNState, mean name, invstd name) per
+    BatchNorm; replay_update=False: none, the pass that filled the cache already counted — `cache_segment` views).
+    The last name is the output: returned as a fresh view of the cached tensor."""
+    if cache is not None and cache.get("y") is not None and cache.get("tag") == tag:
+        if replay_update:
+            for st, mean, invstd in bn:
+                _replay_bn(st, cache[mean], cache[invstd], count, nseg, seg_rev)
+        vals = [cache[k] for k in names]
+        vals[-1] = vals[-1].view_as(vals[-1])
+        return vals
+    if not replay_update:
+        # a `cache_segment` view that cannot be replayed (sub-cache not filled, weights changed since the fill) would be
+        # recomputed HERE with a third running-statistics update the reference never makes — fail instead
+        raise RuntimeError("sivae_hip: replay_update=False needs a filled, current replay cache for this block")
+    return None
+
+
+_BLOCK_CACHED = ("a", "h", "c", "out", "mean1", "invstd1", "mean2", "invstd2", "y")
+
+# ---- the plan of a residual block ------------------------------------------------------------------------------------
+# Every decision ResBlockFn makes, as a function of the block's sizes, the module switches and library predicates that
+# are fixed for the process (`ops._memo`: computed once per block shape).  The forward acts on it and leaves it on ctx,
+# the backward reads it; tests/conv_routes.py maps it to the ops-level calls of the block.
+#   h_saved     h = LeakyReLU(BN1(a)) is written and kept (else: a BatchNorm prologue of conv2 and of its weight gradient)
+#   signmask    the block output is kept as a 1-bit LeakyReLU sign mask
+#   pool_fused  the AvgPool2d after the block is fused into BatchNorm-2's apply
+#   bn2         BatchNorm-2's backward: "signmask" | "dzsum" | "plain"; dy_pooled: it undoes the AvgPool2d while reading
+#               dy; dz_sum: it returns the skip gradient dz as 2x2 block sums
+#   fuse_bn1    conv2's data gradient also reduces BatchNorm-1's backward sums
+#   dgrad1      how conv1's data gradient reaches x: "phase" (x_up: the phase kernel, straight to the low resolution) |
+#               "reduce" (x_up: the full-resolution conv, then 2x2 block sums) | "plain"
+#   skip        where the skip gradient comes from: "expand" (the expand conv's data gradient) | "identity"
+#   skip_sums   ... taken from the 2x2 block sums of dz (a skip behind an Upsample: the expand conv ran at half resolution)
+BlockPlan = collections.namedtuple("BlockPlan", "h_saved signmask pool_fused bn2 dy_pooled dz_sum fuse_bn1 dgrad1 skip "
+                                                "skip_sums")
+
+
+@ops._memo
+def resblock_plan(B, Ci, Cm, Co, H, W, *, x_up, post, nseg, has_exp, training, stored=None):
+    """H, W: the block's resolution (x is stored at half of it with x_up); training: both BatchNorms are;
+    stored: on a replay, (h_saved, signmask) of the pass that filled the cache — the backward must take h and the block
+    output as that pass left them (a `cache_segment` view of a segmented pass is replayed unsegmented)"""
+    c = torch.empty((B, Co, H, W), device="meta")  # (the predicates take the conv output)
+    if stored is not None:
+        h_saved, signmask = stored
+    else:
+        h_saved = MATERIALIZE_H or (nseg > 1 and not ops.seg_prologue_supported(H, W))
+        signmask = bool(training and ops.bn_signmask_supported(c))
+    pool = post == "pool" and not (x_up and not has_exp)
+    up = x_up and post != "pool"  # (the skip was read through upsample addressing: only block sums of dz are needed)
+    if signmask:
+        bn2, dy_pooled, dz_sum = "signmask", pool, up
+    elif up and ops.bn_bwd_dzsum_supported(c):
+        bn2, dy_pooled, dz_sum = "dzsum", False, True
+    else:
+        bn2, dy_pooled, dz_sum = "plain", post == "pool", False
+    phase = bool(x_up and ops.conv2d_up_dgrad_supported(H // 2, W // 2))
+    return BlockPlan(h_saved=bool(h_saved), signmask=signmask,
+                     pool_fused=bool(pool and (signmask or not ((H & 1) or (W & 3)))), bn2=bn2, dy_pooled=bool(dy_pooled),
+                     dz_sum=bool(dz_sum),
+                     fuse_bn1=bool(not h_saved and nseg == 1 and ops.conv2d_dgrad_bnbwd_supported(H, W)),
+                     dgrad1="phase" if phase else ("reduce" if x_up else "plain"),
+                     skip="expand" if has_exp else "identity", skip_sums=bool(x_up and (has_exp or phase or dz_sum)))
+
+
+def _bn2_bwd(plan, d_out, out, c, mean2, invstd2, g2, need_bn2, pg2, nseg):
+    """-> dc, dz (its 2x2 block sums with plan.dz_sum), dgamma2, dbeta2"""
+    if plan.bn2 == "signmask":  # `out` is the LeakyReLU sign mask (1 bit per element)
+        return ops.bn_bwd_signmask(d_out, out, c, mean2, invstd2, g2, SLOPE, dy_pooled=plan.dy_pooled,
+                                   dz_sum=plan.dz_sum, want_param_grads=need_bn2, pg_out=pg2, nseg=nseg)
+    if plan.bn2 == "dzsum":
+        return ops.bn_bwd_dzsum(d_out, out, c, mean2, invstd2, g2, SLOPE, want_param_grads=need_bn2, pg_out=pg2,
+                                nseg=nseg)
+    return ops.bn_bwd(d_out, out, c, mean2, invstd2, g2, SLOPE, want_dz=True, want_param_grads=need_bn2, act_mode=1,
+                      dy_pooled=plan.dy_pooled, pg_out=pg2, nseg=nseg)
+
+
+def _conv1_dgrad(form, da, w1, Ci, out=None):
+    """conv1's data gradient in the plan's `dgrad1` form, written new or accumulated onto `out`"""
+    if form == "phase":
+        return ops.conv2d_up_dgrad(da, packed(w1, 0), Ci, out=out, accumulate=out is not None, wp1=packed(w1, 1))
+    dx = ops.conv2d_fwd(da, packed(w1, 1), Ci, 3, out=out, accumulate=out is not None)
+    return ops.upsample2_bwd(dx) if form == "reduce" else dx  # (adjoint of the deferred Upsample: sum each 2x2 block)
+
+
 class ResBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_exp, w1, g1, b1, w2, g2, b2, st1, st2, post, cache=None, x_up=False, nseg=1, seg_rev=False,
                 replay_update=True):
-        """cache: None, or a dict owned by the caller.  An empty dict is FILLED with this pass's activations;
-        a filled one is REPLAYED: no kernels run except the BatchNorm running-stat updates, the outputs and the
-        tensors saved for backward are the cached ones.  A replay is only valid while x and all weights are unchanged:
-        the weights are checked here (`cache_tag`: torch version counter, optimizer generation, storage) and a stale
-        entry is recomputed; the input is checked once per pass by Decoder.forward.
+        """cache: None, or a dict owned by the caller.  An empty dict is FILLED with this pass's activations; a filled one
+        is REPLAYED (`_replay`): the outputs and the tensors saved for backward are the cached ones.  A replay is only
+        valid while x and all weights are unchanged: the weights are checked here (`cache_tag`) and a stale entry is
+        recomputed; the input is checked once per pass by Decoder.forward.
 
         x_up: x is stored at HALF resolution and stands for Upsample(2,'nearest')(x) (train_soft_intro_vae.py:155):
         every consumer (conv1, conv_expand or the identity add, both weight gradients) reads it through upsample
@@ -302,83 +407,63 @@ class ResBlockFn(torch.autograd.Function):
         nseg > 1: SEGMENTED batch — x holds nseg independent passes of the network (B / nseg images each) laid end to
         end; the convolutions run once over the whole batch, every BatchNorm keeps one set of batch statistics per pass
         (what the reference's separate calls compute, train_soft_intro_vae.py:567-568, :601-608), the running buffers
-        are updated once per pass in pass order (seg_rev: last segment first).
-        replay_update=False: a replay leaves the running buffers alone (the pass that filled the cache already counted:
-        `cache_segment` views)."""
+        are updated once per pass in pass order (seg_rev: last segment first).  replay_update: see `_replay`."""
         x = x.contiguous()
         _claim(ctx, ((1, w_exp), (2, w1), (3, g1), (4, b1), (5, w2), (6, g2), (7, b2)))
         B, Ci, H, W = x.shape
         if x_up:
             H, W = 2 * H, 2 * W
-        ctx.x_up = x_up
         Cm, Co = w1.shape[0], w2.shape[0]
         tag = cache_tag((w_exp, w1, g1, b1, w2, g2, b2))
-        if cache is not None and cache.get("y") is not None and cache.get("tag") == tag:
-            a, h, c, out, mean1, invstd1, mean2, invstd2, y = (cache[k] for k in (
-                "a", "h", "c", "out", "mean1", "invstd1", "mean2", "invstd2", "y"))
-            if replay_update:
-                _replay_bn(st1, mean1, invstd1, (B // nseg) * H * W, nseg, seg_rev)
-                _replay_bn(st2, mean2, invstd2, (B // nseg) * H * W, nseg, seg_rev)
-            ctx.nseg = nseg
-            ctx.post = post
-            ctx.has_exp = w_exp is not None
-            ctx.training = st1.training and st2.training
-            ctx.save_for_backward(x, a, h, c, out, mean1, invstd1, mean2, invstd2, w_exp, w1, g1, b1, w2, g2, b2)
-            return y.view_as(y)
-        if not replay_update:
-            # a `cache_segment` view that cannot be replayed (sub-cache not filled, weights changed since the fill) would be
-            # recomputed HERE with a third running-statistics update the reference never makes — fail instead
-            raise RuntimeError("sivae_hip: replay_update=False needs a filled, current replay cache for this block")
-        idt = x
-        if w_exp is not None:
-            # a 1x1 conv commutes with nearest upsampling pixel for pixel (bit-exactly): with x_up it runs on the
-            # half-resolution tensor (1/4 of the FLOPs and output bytes) and the residual add reads it through
-            # upsample addressing like an identity skip
-            idt = ops.conv2d_fwd(x, packed(w_exp, 0), Co, 1)
-        if st1.training:
-            a, p1 = ops.conv2d_fwd(x, packed(w1, 0), Cm, 3, want_stats=True, upsample=x_up, nseg=nseg)
+        hit = _replay(cache, tag, _BLOCK_CACHED, ((st1, "mean1", "invstd1"), (st2, "mean2", "invstd2")),
+                      (B // nseg) * H * W, nseg, seg_rev, replay_update)
+        plan = resblock_plan(B, Ci, Cm, Co, H, W, x_up=x_up, post=post, nseg=nseg, has_exp=w_exp is not None,
+                             training=st1.training and st2.training, stored=None if hit is None else cache["form"])
+        if hit is not None:
+            a, h, c, out, mean1, invstd1, mean2, invstd2, y = hit
         else:
-            a, p1 = ops.conv2d_fwd(x, packed(w1, 0), Cm, 3, upsample=x_up), None
-        mean1, invstd1 = _stats(p1, B, Cm, H * W, st1, nseg, seg_rev)
-        if MATERIALIZE_H or (nseg > 1 and not ops.seg_prologue_supported(H, W)):
-            # h = LeakyReLU(BN1(a)) written once (2 HBM passes over a Cm-channel tensor) and kept for backward
-            # (segmented batches on the 4x4 / 8x8 maps: the kernels that take those maps have no per-segment prologue)
-            h = ops.bn_apply_act(a, None, mean1, invstd1, g1.detach(), b1.detach(), SLOPE, nseg=nseg)
-            pro1 = None
-        else:
-            h = a
-            pro1 = (mean1, invstd1, g1.detach(), b1.detach(), SLOPE)
-        if st2.training:
-            c, p2 = ops.conv2d_fwd(h, packed(w2, 0), Co, 3, pro=pro1, want_stats=True, nseg=nseg)
-        else:
-            c, p2 = ops.conv2d_fwd(h, packed(w2, 0), Co, 3, pro=pro1, nseg=nseg), None
-        mean2, invstd2 = _stats(p2, B, Co, H * W, st2, nseg, seg_rev)
-        fused = None
-        pool_fusable = post == "pool" and not (x_up and w_exp is None)
-        if st1.training and st2.training and ops.bn_signmask_supported(c):
-            # the backward takes the LeakyReLU sign from a 1-bit mask written here, not from the output: `out` below
-            # is that mask (uint8), and a pooled block never writes its full-resolution output
-            full, y, out = ops.bn_apply_act_signmask(c, idt, mean2, invstd2, g2.detach(), b2.detach(), SLOPE,
-                                                     res_up=x_up, pool=pool_fusable, want_full=not pool_fusable,
-                                                     nseg=nseg)
-            if not pool_fusable:
-                y = _post_fwd(full, post)
-            del full
-        else:
-            if pool_fusable:
-                fused = ops.bn_apply_act_pool(c, idt, mean2, invstd2, g2.detach(), b2.detach(), SLOPE, nseg=nseg)
-            if fused is not None:
-                out, y = fused  # BatchNorm + residual + LeakyReLU and the AvgPool2d that follows, one pass
+            idt = x
+            if w_exp is not None:
+                # a 1x1 conv commutes with nearest upsampling pixel for pixel (bit-exactly): with x_up it runs on the
+                # half-resolution tensor (1/4 of the FLOPs and output bytes) and the residual add reads it through
+                # upsample addressing like an identity skip
+                idt = ops.conv2d_fwd(x, packed(w_exp, 0), Co, 1)
+            if st1.training:
+                a, p1 = ops.conv2d_fwd(x, packed(w1, 0), Cm, 3, want_stats=True, upsample=x_up, nseg=nseg)
             else:
-                out = ops.bn_apply_act(c, idt, mean2, invstd2, g2.detach(), b2.detach(), SLOPE, res_up=x_up, nseg=nseg)
+                a, p1 = ops.conv2d_fwd(x, packed(w1, 0), Cm, 3, upsample=x_up), None
+            mean1, invstd1 = _stats(p1, B, Cm, H * W, st1, nseg, seg_rev)
+            if plan.h_saved:
+                # h = LeakyReLU(BN1(a)) written once (2 HBM passes over a Cm-channel tensor) and kept for backward
+                # (segmented batches on the 4x4 / 8x8 maps: the kernels that take those maps have no per-segment prologue)
+                h = ops.bn_apply_act(a, None, mean1, invstd1, g1.detach(), b1.detach(), SLOPE, nseg=nseg)
+                pro1 = None
+            else:
+                h = a
+                pro1 = (mean1, invstd1, g1.detach(), b1.detach(), SLOPE)
+            if st2.training:
+                c, p2 = ops.conv2d_fwd(h, packed(w2, 0), Co, 3, pro=pro1, want_stats=True, nseg=nseg)
+            else:
+                c, p2 = ops.conv2d_fwd(h, packed(w2, 0), Co, 3, pro=pro1, nseg=nseg), None
+            mean2, invstd2 = _stats(p2, B, Co, H * W, st2, nseg, seg_rev)
+            bn2 = (c, idt, mean2, invstd2, g2.detach(), b2.detach(), SLOPE)
+            if plan.signmask:
+                # the backward takes the LeakyReLU sign from a 1-bit mask written here, not from the output: `out` below
+                # is that mask (uint8), and a pooled block never writes its full-resolution output
+                full, y, out = ops.bn_apply_act_signmask(*bn2, res_up=x_up, pool=plan.pool_fused,
+                                                         want_full=not plan.pool_fused, nseg=nseg)
+                if not plan.pool_fused:
+                    y = _post_fwd(full, post)
+                del full
+            elif plan.pool_fused:
+                out, y = ops.bn_apply_act_pool(*bn2, nseg=nseg)  # ... and the AvgPool2d that follows, one pass
+            else:
+                out = ops.bn_apply_act(*bn2, res_up=x_up, nseg=nseg)
                 y = _post_fwd(out, post)
-        if cache is not None:
-            cache.update(a=a, h=h, c=c, out=out, mean1=mean1, invstd1=invstd1, mean2=mean2, invstd2=invstd2, y=y,
-                         tag=tag)
-        ctx.nseg = nseg
-        ctx.post = post
-        ctx.has_exp = w_exp is not None
-        ctx.training = st1.training and st2.training
+            if cache is not None:
+                cache.update(a=a, h=h, c=c, out=out, mean1=mean1, invstd1=invstd1, mean2=mean2, invstd2=invstd2, y=y,
+                             tag=tag, form=(plan.h_saved, plan.signmask))
+        ctx.plan, ctx.nseg, ctx.post, ctx.x_up, ctx.training = plan, nseg, post, x_up, st1.training and st2.training
         ctx.save_for_backward(x, a, h, c, out, mean1, invstd1, mean2, invstd2, w_exp, w1, g1, b1, w2, g2, b2)
         return y
 
@@ -388,118 +473,65 @@ class ResBlockFn(torch.autograd.Function):
             raise RuntimeError("sivae_hip: backward through eval-mode BatchNorm is not supported")
         x, a, h, c, out, mean1, invstd1, mean2, invstd2, w_exp, w1, g1, b1, w2, g2, b2 = ctx.saved_tensors
         k_we, k_w1, k_g1, k_b1, k_w2, k_g2, k_b2 = ctx.use
-        nseg = ctx.nseg
-        h_saved = h.data_ptr() != a.data_ptr()
+        plan, nseg, x_up = ctx.plan, ctx.nseg, ctx.x_up
         need = ctx.needs_input_grad
         need_x, need_we, need_w1, need_bn1, need_w2, need_bn2 = need[0], need[1], need[2], need[3] or need[4], \
             need[5], need[6] or need[7]
-        Cm = w1.shape[0]
-        # BN2 + residual + LeakyReLU; the AvgPool2d that follows an encoder block is undone while reading dy
-        x_up = ctx.x_up
+        Ci, Cm = x.shape[1], w1.shape[0]
         pg2 = _pg_dst(g2, k_g2, b2, k_b2) if need_bn2 else None
         pg1 = _pg_dst(g1, k_g1, b1, k_b1) if need_bn1 else None
-        dzh = None  # 2x2 block sums of dz: all a block behind an Upsample ever needs of it
-        if out.dtype == torch.uint8:  # `out` is the LeakyReLU sign mask (1 bit per element)
-            if ctx.post == "pool" and not (x_up and not ctx.has_exp):
-                dc, dz, dg2, db2 = ops.bn_bwd_signmask(dy.contiguous(), out, c, mean2, invstd2, g2, SLOPE,
-                                                       dy_pooled=True, want_param_grads=need_bn2, pg_out=pg2,
-                                                       nseg=nseg)
-            else:
-                d_out = _post_bwd(dy.contiguous(), ctx.post, c.shape)
-                want_sum = x_up and ctx.post != "pool"
-                dc, dz, dg2, db2 = ops.bn_bwd_signmask(d_out, out, c, mean2, invstd2, g2, SLOPE, dz_sum=want_sum,
-                                                       want_param_grads=need_bn2, pg_out=pg2, nseg=nseg)
-                if want_sum:
-                    dzh, dz = dz, None
-                del d_out
-        elif x_up and ctx.post != "pool" and ops.bn_bwd_dzsum_supported(c):
-            d_out = _post_bwd(dy.contiguous(), ctx.post, out.shape)
-            dc, dzh, dg2, db2 = ops.bn_bwd_dzsum(d_out, out, c, mean2, invstd2, g2, SLOPE, want_param_grads=need_bn2,
-                                                 pg_out=pg2, nseg=nseg)
-            dz = None
-            del d_out
-        elif ctx.post == "pool":
-            dc, dz, dg2, db2 = ops.bn_bwd(dy.contiguous(), out, c, mean2, invstd2, g2, SLOPE, want_dz=True,
-                                          want_param_grads=need_bn2, act_mode=1, dy_pooled=True, pg_out=pg2, nseg=nseg)
-        else:
-            d_out = _post_bwd(dy.contiguous(), ctx.post, out.shape)
-            dc, dz, dg2, db2 = ops.bn_bwd(d_out, out, c, mean2, invstd2, g2, SLOPE, want_dz=True,
-                                          want_param_grads=need_bn2, act_mode=1, pg_out=pg2, nseg=nseg)
-            del d_out
-        pro1 = None if h_saved else (mean1, invstd1, g1, b1, SLOPE)
-        if pg2 is not None:
-            _done(g2, b2)
-        dw2 = ops.conv2d_wgrad(h, dc, 3, pro=pro1, out=_dst(w2, k_w2), nseg=nseg) if need_w2 else None
-        if need_w2 and k_w2 >= 0:
-            _done(w2)
-        fuse_bn1 = (not h_saved) and nseg == 1 and ops.conv2d_dgrad_bnbwd_supported(dc.shape[2], dc.shape[3])
-        if fuse_bn1:
+        # BN2 + residual + LeakyReLU; the AvgPool2d that follows an encoder block is undone while reading dy
+        d_out = dy.contiguous() if plan.dy_pooled else _post_bwd(dy.contiguous(), ctx.post, c.shape)
+        dc, dz, dg2, db2 = _bn2_bwd(plan, d_out, out, c, mean2, invstd2, g2, need_bn2, pg2, nseg)
+        del d_out
+        dg2, db2 = _hand_bn(pg2, g2, b2, dg2, db2, need[6], need[7])
+        pro1 = None if plan.h_saved else (mean1, invstd1, g1, b1, SLOPE)
+        dw2 = _hand(ops.conv2d_wgrad(h, dc, 3, pro=pro1, out=_dst(w2, k_w2), nseg=nseg) if need_w2 else None, w2, k_w2)
+        if plan.fuse_bn1:
             # conv2's data gradient also reduces BatchNorm-1's backward sums in its epilogue (one pass fewer over dh, a)
             dh, part1 = ops.conv2d_dgrad_bnbwd(dc, packed(w2, 1), Cm, a, mean1, invstd1, g1, b1, SLOPE)
         else:
             dh = ops.conv2d_fwd(dc, packed(w2, 1), Cm, 3)
         del dc
         # BN1 + LeakyReLU (sign from the saved h, or recomputed from a when h was never stored)
-        if fuse_bn1:
+        if plan.fuse_bn1:
             da, dg1, db1 = ops.bn_bwd_from_partials(dh, a, mean1, invstd1, g1, b1, part1, SLOPE,
                                                     want_param_grads=need_bn1, pg_out=pg1)
-        elif h_saved:
-            da, _, dg1, db1 = ops.bn_bwd(dh, h, a, mean1, invstd1, g1, SLOPE, want_dz=False,
-                                         want_param_grads=need_bn1, act_mode=1, pg_out=pg1, nseg=nseg)
         else:
-            da, _, dg1, db1 = ops.bn_bwd(dh, None, a, mean1, invstd1, g1, SLOPE, want_dz=False,
-                                         want_param_grads=need_bn1, beta=b1, act_mode=2, pg_out=pg1, nseg=nseg)
+            da, _, dg1, db1 = ops.bn_bwd(dh, h if plan.h_saved else None, a, mean1, invstd1, g1, SLOPE, want_dz=False,
+                                         want_param_grads=need_bn1, beta=None if plan.h_saved else b1,
+                                         act_mode=1 if plan.h_saved else 2, pg_out=pg1, nseg=nseg)
         del dh
-        if pg1 is not None:
-            _done(g1, b1)
-        dw1 = ops.conv2d_wgrad(x, da, 3, upsample=x_up, out=_dst(w1, k_w1)) if need_w1 else None
-        if need_w1 and k_w1 >= 0:
-            _done(w1)
-        dwe = None
+        dg1, db1 = _hand_bn(pg1, g1, b1, dg1, db1, need[3], need[4])
+        dw1 = _hand(ops.conv2d_wgrad(x, da, 3, upsample=x_up, out=_dst(w1, k_w1)) if need_w1 else None, w1, k_w1)
+        # dx = conv1's data gradient (plan.dgrad1) + the skip gradient (plan.skip): dz, or — behind an Upsample, where the
+        # expand conv ran at half resolution and the phase kernel writes at half resolution — its 2x2 block sums
+        if plan.skip_sums and not plan.dz_sum and (need_x or need_we):
+            dz = ops.upsample2_bwd(dz)
+        dwe = ops.conv2d_wgrad(x, dz, 1, out=_dst(w_exp, k_we)) if need_we else None
         dx = None
-        # conv1's data gradient straight to the low-resolution x (phase-folded F(2x2,2x2) kernel)
-        up_dg = x_up and ops.conv2d_up_dgrad_supported(x.shape[2], x.shape[3])
-        if ctx.has_exp and x_up:
-            # the expand conv ran at half resolution: its gradients do too (dz summed over each 2x2 block first)
-            if dzh is None:
-                dzh = ops.upsample2_bwd(dz) if (need_we or need_x) else None
-            if need_we:
-                dwe = ops.conv2d_wgrad(x, dzh, 1, out=_dst(w_exp, k_we))
-            if need_x:
-                if up_dg:
-                    dx = ops.conv2d_up_dgrad(da, packed(w1, 0), x.shape[1], wp1=packed(w1, 1))
-                else:
-                    dx = ops.upsample2_bwd(ops.conv2d_fwd(da, packed(w1, 1), x.shape[1], 3))
-                ops.conv2d_fwd(dzh, packed(w_exp, 1), x.shape[1], 1, out=dx, accumulate=True)
-        elif up_dg and need_x:
-            dx = dzh if dzh is not None else ops.upsample2_bwd(dz)  # identity branch, already at low resolution
-            ops.conv2d_up_dgrad(da, packed(w1, 0), x.shape[1], out=dx, accumulate=True, wp1=packed(w1, 1))
-        elif x_up and dzh is not None and dz is None:
+        if need_x and plan.skip == "expand":
+            dx = _conv1_dgrad(plan.dgrad1, da, w1, Ci)
+            ops.conv2d_fwd(dz, packed(w_exp, 1), Ci, 1, out=dx, accumulate=True)
+        elif need_x and plan.dgrad1 == "reduce" and plan.skip_sums:
             # identity skip behind an Upsample on a map the phase kernel does not take: reduce conv1's full-resolution
             # data gradient, then add the (already reduced) skip gradient
-            if need_x:
-                dx = ops.upsample2_bwd(ops.conv2d_fwd(da, packed(w1, 1), x.shape[1], 3))
-                ops.add_(dx, dzh)
-        else:
-            if ctx.has_exp:
-                if need_we:
-                    dwe = ops.conv2d_wgrad(x, dz, 1, out=_dst(w_exp, k_we))
-                if need_x:
-                    dx = ops.conv2d_fwd(da, packed(w1, 1), x.shape[1], 3)
-                    ops.conv2d_fwd(dz, packed(w_exp, 1), x.shape[1], 1, out=dx, accumulate=True)
-            elif need_x:
-                dx = dz  # identity branch gradient; add the conv1 branch on top
-                ops.conv2d_fwd(da, packed(w1, 1), x.shape[1], 3, out=dx, accumulate=True)
-            if x_up and dx is not None:
-                dx = ops.upsample2_bwd(dx)  # adjoint of the deferred Upsample: sum each 2x2 block
-        if need_we and ctx.has_exp and k_we >= 0:
-            _done(w_exp)
-        # (gradients that went into a slab are not handed to autograd)
-        return (dx, dwe if k_we < 0 else None, dw1 if k_w1 < 0 else None,
-                dg1 if (need[3] and pg1 is None) else None, db1 if (need[4] and pg1 is None) else None,
-                dw2 if k_w2 < 0 else None,
-                dg2 if (need[6] and pg2 is None) else None, db2 if (need[7] and pg2 is None) else None,
-                None, None, None, None, None, None, None, None)
+            dx = _conv1_dgrad("reduce", da, w1, Ci)
+            ops.add_(dx, dz)
+        elif need_x:
+            dx = _conv1_dgrad(plan.dgrad1, da, w1, Ci, out=dz)  # identity branch gradient; the conv1 branch on top
+        return (dx, _hand(dwe, w_exp, k_we), dw1, dg1, db1, dw2, dg2, db2, None, None, None, None, None, None, None, None)
+
+
+def stem_edge5(w):
+    """the stem's 5x5 layer with <= 3 image channels: the edge kernels take its weight and data gradients"""
+    return _is_edge5(w) and w.shape[1] <= 3
+
+
+def predict_edge5(w):
+    """-> (forward, weight gradient) of predict's 5x5 layer run on the edge kernels (the forward with <= 3 image
+    channels only; the data gradient never does)"""
+    return _is_edge5(w) and w.shape[0] <= 3, _is_edge5(w)
 
 
 class StemFn(torch.autograd.Function):
@@ -539,21 +571,17 @@ class StemFn(torch.autograd.Function):
         da, _, dg, db = ops.bn_bwd(dy.contiguous(), None, a, mean, invstd, g, SLOPE, want_dz=False,
                                    want_param_grads=need[2] or need[3], beta=b, act_mode=2, dy_pooled=True,
                                    pg_out=pg, nseg=ctx.nseg)
-        edge = _is_edge5(w) and w.shape[1] <= 3
+        edge = stem_edge5(w)
         dw = None
         if need[1]:
             dst = _dst(w, k_w)
-            dw = ops.conv5_edge_wgrad(x, da, out=dst) if edge else ops.conv2d_wgrad(x, da, 5, out=dst)
-            if dst is not None:
-                _done(w)
-        if pg is not None:
-            _done(g, b)
+            dw = _hand(ops.conv5_edge_wgrad(x, da, out=dst) if edge else ops.conv2d_wgrad(x, da, 5, out=dst), w, k_w)
+        dg, db = _hand_bn(pg, g, b, dg, db, need[2], need[3])
         dx = None
         if need[0]:
             dx = (ops.conv5_smallco_fwd(da, packed5(w, 1), x.shape[1]) if edge
                   else ops.conv2d_fwd(da, packed(w, 1), x.shape[1], 5))
-        return (dx, dw if k_w < 0 else None, dg if (need[2] and pg is None) else None,
-                db if (need[3] and pg is None) else None, None, None, None)
+        return dx, dw, dg, db, None, None, None
 
 
 class ConvBiasFn(torch.autograd.Function):
@@ -563,17 +591,16 @@ class ConvBiasFn(torch.autograd.Function):
     def forward(ctx, x, w, bias, cache=None):
         x = x.contiguous()
         _claim(ctx, ((1, w), (2, bias)))
-        ks = w.shape[2]
         ctx.save_for_backward(x, w, bias)
-        ctx.has_bias = bias is not None
         tag = cache_tag((w, bias))
-        if cache is not None and cache.get("y") is not None and cache.get("tag") == tag:
-            return cache["y"].view_as(cache["y"])
+        hit = _replay(cache, tag, ("y",))
+        if hit is not None:
+            return hit[0]
         b_ = None if bias is None else bias.detach()
-        if _is_edge5(w) and w.shape[0] <= 3:
+        if predict_edge5(w)[0]:
             y = ops.conv5_smallco_fwd(x, packed5(w, 0), w.shape[0], bias=b_)
         else:
-            y = ops.conv2d_fwd(x, packed(w, 0), w.shape[0], ks, bias=b_)
+            y = ops.conv2d_fwd(x, packed(w, 0), w.shape[0], w.shape[2], bias=b_)
         if cache is not None:
             cache["y"], cache["tag"] = y, tag
         return y
@@ -588,11 +615,11 @@ class ConvBiasFn(torch.autograd.Function):
         dw = None
         if need[1]:
             dst = _dst(w, k_w)
-            dw = ops.conv5_edge_wgrad(x, dy, out=dst) if _is_edge5(w) else ops.conv2d_wgrad(x, dy, ks, out=dst)
-        db = ops.channel_sum(dy, out=_dst(bias, k_b)) if (ctx.has_bias and need[2]) else None
-        _done(w if (need[1] and k_w >= 0) else None, bias if (db is not None and k_b >= 0) else None)
+            dw = ops.conv5_edge_wgrad(x, dy, out=dst) if predict_edge5(w)[1] else ops.conv2d_wgrad(x, dy, ks, out=dst)
+        db = ops.channel_sum(dy, out=_dst(bias, k_b)) if (bias is not None and need[2]) else None
+        dw, db = _hand(dw, w, k_w), _hand(db, bias, k_b)
         dx = ops.conv2d_fwd(dy, packed(w, 1), x.shape[1], ks) if need[0] else None
-        return dx, dw if k_w < 0 else None, db if k_b < 0 else None, None
+        return dx, dw, db, None
 
 
 class LinearFn(torch.autograd.Function):
@@ -619,7 +646,6 @@ class LinearFn(torch.autograd.Function):
             if relu:
                 ops.relu_fwd(y, inplace=True)
         ctx.relu = relu
-        ctx.has_bias = bias is not None
         ctx.save_for_backward(x, w, y if relu else None, bias)
         return y
 
@@ -634,7 +660,7 @@ class LinearFn(torch.autograd.Function):
         B, K = x.shape
         N = w.shape[0]
         dy4 = dy.view(B, N, 1, 1)
-        db = ops.channel_sum(dy4, out=_dst(bias, k_b)) if (ctx.has_bias and need[2]) else None
+        db = ops.channel_sum(dy4, out=_dst(bias, k_b)) if (bias is not None and need[2]) else None
         dst = _dst(w, k_w) if need[1] else None
         if ctx.fast:
             dw = ops.linear_wgrad(dy, x, out=dst) if need[1] else None
@@ -645,8 +671,7 @@ class LinearFn(torch.autograd.Function):
                 dw = ops.conv2d_wgrad(x.view(B, K, 1, 1), dy4, 1, out=None if dst is None else dst.view(N, K, 1, 1))
                 dw = dw.view(N, K)
             dx = ops.conv2d_fwd(dy4, packed(w, 1), K, 1).view(B, K) if need[0] else None
-        _done(w if (need[1] and k_w >= 0) else None, bias if (db is not None and k_b >= 0) else None)
-        return dx, dw if k_w < 0 else None, db if k_b < 0 else None, None
+        return dx, _hand(dw, w, k_w), _hand(db, bias, k_b), None
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -787,7 +812,7 @@ def cache_segment(cache, g, nseg):
     activations / statistics restricted to that pass's images, usable as the cache of an UNsegmented replay.  The
     engine builds the autograd graph of ONE pass of a pair this way (E-step: `rec` needs a data gradient, `fake` has no
     graph at all — reference :557-561) after the pair ran as one batch without a graph."""
-    def cut(t, n_rows=None):
+    def cut(t):
         if t is None:
             return None
         n = t.shape[0] // nseg
@@ -802,6 +827,8 @@ def cache_segment(cache, g, nseg):
         for name in ("a", "h", "c", "out", "mean1", "invstd1", "mean2", "invstd2"):
             if name in sub:
                 v[name] = cut(sub[name])
+        if "form" in sub:
+            v["form"] = sub["form"]
         out[k] = v
     return out
 
@@ -834,3 +861,7 @@ def kl(logvar, mu, mu_o=0.0, logvar_o=0.0, reduce="none"):
 
 def expelbo(L, KL, scale, beta_rec, beta_neg):
     return ExpElboFn.apply(L, KL, float(scale), float(beta_rec), float(beta_neg))
+
+
+# (assigning a switch of this module forgets the memoised plans, like a switch of `ops` does)
+sys.modules[__name__].__class__ = ops._SwitchWatch

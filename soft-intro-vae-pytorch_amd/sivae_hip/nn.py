@@ -8,6 +8,7 @@ parameter/buffer containers (they give the reference's default initialisation an
 forward() is never called; Encoder/Decoder/ResidualBlock.forward dispatch to the HIP blocks.
 """
 import os
+import sys
 
 import torch
 import torch.nn as nn
@@ -263,3 +264,7 @@ class Decoder(nn.Module):
         if self.compute_dtype == "bf16":
             y = SF16.to_blocked(y)
         return _run_main(self.main, y, cache, nseg=nseg, seg_rev=seg_rev, replay_update=replay_update)
+
+
+# (assigning a switch of this module forgets the memoised routes and block plans, like a switch of `ops` does)
+sys.modules[__name__].__class__ = SF.ops._SwitchWatch

@@ -7,6 +7,7 @@ gradients, weights and weight gradients are float32.  Like `ops`, everything lau
 tensor's device and there is no CPU path.
 """
 import os
+import sys
 
 import torch
 
@@ -288,3 +289,7 @@ def add_(y, x):
     assert y.shape == x.shape
     _lib.call("sivae_bf16_add_inplace", _p(y), _p(x), y.numel() // 8, _s(y))
     return y
+
+
+# (assigning a switch of this module forgets the memoised routes and block plans, like a switch of `ops` does)
+sys.modules[__name__].__class__ = ops._SwitchWatch

@@ -206,17 +206,14 @@ def block_route(B, nseg, Ci, Cm, Co, H, W, x_up, post, bn_fused=True, pool_dgrad
     """route class of a ResidualBlock call from the library's predicates:
     (has_exp, x_up, post, conv1 tile, conv2 tile, pooled data gradient (x_up only), BN-1 / BN-2 one-launch backward,
     segmented)"""
-    from sivae_hip import lib, ops16
+    from sivae_hip import functional16 as SF16
+    from sivae_hip import lib
     L = lib.load()
     seg = B // nseg
     pool = None
     if x_up:
-        old = ops16.POOL_DGRAD
-        ops16.POOL_DGRAD = old and pool_dgrad
-        try:
-            pool = bool(ops16.conv2d_pool_supported(B, Cm, Ci, H, W, 3))
-        finally:
-            ops16.POOL_DGRAD = old
+        plan = SF16.resblock_plan16(B, Ci, Cm, Co, H, W, x_up=x_up, post=post, nseg=nseg, has_exp=Ci != Co, training=True)
+        pool = bool(pool_dgrad and plan.dx == "pool")
     f1 = bool(bn_fused and L.sivae_bf16_bn_bwd_fused_seg_supported(B, Cm, H, W, seg) == 1)
     f2 = bool(bn_fused and L.sivae_bf16_bn_bwd_fused_seg_supported(B, Co, H, W, seg) == 1)
     return ("block", Ci != Co, bool(x_up), post, _tile(L, B, Ci, Cm, H, W), _tile(L, B, Cm, Co, H, W), pool, f1, f2,

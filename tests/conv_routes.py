@@ -325,7 +325,9 @@ NETWORKS = [("celeb256_bs128", [64, 128, 256, 512, 512, 512], 256, 128),
 
 def block_cases(ops, B, Ci, Cm, Co, H, W, x_up, post, nseg, has_exp):
     """the ops-level calls of one training-mode functional.ResBlockFn forward + backward (every gradient needed,
-    parameter gradients written into slabs), in its order; H, W: the block's resolution"""
+    parameter gradients written into slabs), in its order — read off the block's plan; H, W: the block's resolution"""
+    from sivae_hip import functional as SF
+    plan = SF.resblock_plan(B, Ci, Cm, Co, H, W, x_up=x_up, post=post, nseg=nseg, has_exp=has_exp, training=True)
     out = []
 
     def add(kind, **p):
@@ -335,44 +337,33 @@ def block_cases(ops, B, Ci, Cm, Co, H, W, x_up, post, nseg, has_exp):
     if has_exp:
         add("fwd", B=B, Ci=Ci, Co=Co, H=Hs, W=Ws, ks=1)
     add("fwd", B=B, Ci=Ci, Co=Cm, H=H, W=W, ks=3, want_stats=True, upsample=x_up, nseg=nseg)
-    h_saved = nseg > 1 and not ops.seg_prologue_supported(H, W)
-    add("fwd", B=B, Ci=Cm, Co=Co, H=H, W=W, ks=3, pro=not h_saved, want_stats=True, nseg=nseg)
-    c = M(B, Co, H, W)
-    pooled = post == "pool" and not (x_up and not has_exp)
-    dzh = False
-    if ops.bn_signmask_supported(c):
-        dzh = (not pooled) and x_up and post != "pool"
-        add("bn_signmask", B=B, C=Co, H=H, W=W, dy_pooled=pooled, dz_sum=dzh, nseg=nseg)
-    elif x_up and post != "pool" and ops.bn_bwd_dzsum_supported(c):
-        dzh = True
+    add("fwd", B=B, Ci=Cm, Co=Co, H=H, W=W, ks=3, pro=not plan.h_saved, want_stats=True, nseg=nseg)
+    if plan.bn2 == "signmask":
+        add("bn_signmask", B=B, C=Co, H=H, W=W, dy_pooled=plan.dy_pooled, dz_sum=plan.dz_sum, nseg=nseg)
+    elif plan.bn2 == "dzsum":
         add("bn_dzsum", B=B, C=Co, H=H, W=W, nseg=nseg)
     else:
-        add("bn_bwd", B=B, C=Co, H=H, W=W, act=1, want_dz=True, dy_pooled=post == "pool", has_pg_out=True, nseg=nseg)
-    add("wgrad", B=B, Ci=Cm, Co=Co, H=H, W=W, ks=3, pro=not h_saved, has_out=True, nseg=nseg)
-    if (not h_saved) and nseg == 1 and ops.conv2d_dgrad_bnbwd_supported(H, W):
+        add("bn_bwd", B=B, C=Co, H=H, W=W, act=1, want_dz=True, dy_pooled=plan.dy_pooled, has_pg_out=True, nseg=nseg)
+    add("wgrad", B=B, Ci=Cm, Co=Co, H=H, W=W, ks=3, pro=not plan.h_saved, has_out=True, nseg=nseg)
+    if plan.fuse_bn1:
         add("dgrad_bnbwd", B=B, Ci=Co, Cm=Cm, H=H, W=W)
     else:
         add("fwd", B=B, Ci=Co, Co=Cm, H=H, W=W, ks=3, mode=1)
-        add("bn_bwd", B=B, C=Cm, H=H, W=W, act=1 if h_saved else 2, has_pg_out=True, nseg=nseg)
+        add("bn_bwd", B=B, C=Cm, H=H, W=W, act=1 if plan.h_saved else 2, has_pg_out=True, nseg=nseg)
     add("wgrad", B=B, Ci=Ci, Co=Cm, H=H, W=W, ks=3, upsample=x_up, has_out=True)
-    up_dg = x_up and ops.conv2d_up_dgrad_supported(Hs, Ws)
-    if has_exp and x_up:
-        add("wgrad", B=B, Ci=Ci, Co=Co, H=Hs, W=Ws, ks=1, has_out=True)
-        if up_dg:
-            add("up_dgrad", B=B, C=Cm, N=Ci, H=H, W=W, has_wp1=True)
-        else:
-            add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1)
-        add("fwd", B=B, Ci=Co, Co=Ci, H=Hs, W=Ws, ks=1, mode=1, has_out=True, accumulate=True)
-    elif up_dg:
-        add("up_dgrad", B=B, C=Cm, N=Ci, H=H, W=W, has_wp1=True, has_out=True, accumulate=True)
-    elif x_up and dzh:
-        add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1)
-    elif has_exp:
-        add("wgrad", B=B, Ci=Ci, Co=Co, H=H, W=W, ks=1, has_out=True)
-        add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1)
-        add("fwd", B=B, Ci=Co, Co=Ci, H=H, W=W, ks=1, mode=1, has_out=True, accumulate=True)
+    # the skip gradient is read at x's resolution when only its 2x2 block sums are needed
+    Hz, Wz = (Hs, Ws) if plan.skip_sums else (H, W)
+    if plan.skip == "expand":
+        add("wgrad", B=B, Ci=Ci, Co=Co, H=Hz, W=Wz, ks=1, has_out=True)
+    # conv1's data gradient: onto the skip gradient of an identity skip, unless both are reduced separately
+    onto = {} if (plan.skip == "expand" or (plan.dgrad1 == "reduce" and plan.skip_sums)) else dict(has_out=True,
+                                                                                                  accumulate=True)
+    if plan.dgrad1 == "phase":
+        add("up_dgrad", B=B, C=Cm, N=Ci, H=H, W=W, has_wp1=True, **onto)
     else:
-        add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1, has_out=True, accumulate=True)
+        add("fwd", B=B, Ci=Cm, Co=Ci, H=H, W=W, ks=3, mode=1, **onto)
+    if plan.skip == "expand":
+        add("fwd", B=B, Ci=Co, Co=Ci, H=Hz, W=Wz, ks=1, mode=1, has_out=True, accumulate=True)
     return out
 
 
@@ -401,16 +392,17 @@ def network_cases(ops, channels, image_size, B, nseg=1, cdim=3):
         out.append((where[0] + ".stem", "fwd", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=5, want_stats=True)))
         out.append((where[0] + ".stem", "bn_bwd", dict(B=Bx, C=Co, H=H, W=W, act=2, dy_pooled=True, has_pg_out=True,
                                                        nseg=nseg)))
-        if not (SF._is_edge5(w) and Ci <= 3):
+        if not SF.stem_edge5(w):
             out.append((where[0] + ".stem", "wgrad", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=5, has_out=True)))
         return M(Bx, Co, H // 2, W // 2)
 
     def conv_bias(x, w, bias, cache=None):
         Bx, Ci, H, W = x.shape
         Co, ks = w.shape[0], w.shape[2]
-        if not (SF._is_edge5(w) and Co <= 3):
+        edge_fwd, edge_wgrad = SF.predict_edge5(w)
+        if not edge_fwd:
             out.append((where[0] + ".predict", "fwd", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=ks, bias=bias is not None)))
-        if not SF._is_edge5(w):
+        if not edge_wgrad:
             out.append((where[0] + ".predict", "wgrad", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=ks, has_out=True)))
         out.append((where[0] + ".predict", "fwd", dict(B=Bx, Ci=Co, Co=Ci, H=H, W=W, ks=ks, mode=1)))
         return M(Bx, Co, H, W)
