@@ -684,6 +684,39 @@ int sivae_conv2d_wino4_wgrad(const float* x, const float* dy, float* dw, const f
                              const float* pro_gamma, const float* pro_beta, float pro_slope, int B, int Ci, int Co, int H,
                              int W, int seg_images, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
 
+/* ---- point clouds: the 3-D Soft-IntroVAE (pointcloud.hip) ------------------------------------------------------
+ * ChamferLoss.forward (soft_intro_vae_3d/losses/chamfer_loss.py:11-17): preds [B][M][3], gts [B][N][3] ->
+ * loss[b] = sum_j min_i |G_i - P_j|^2 + sum_i min_j |G_i - P_j|^2, both directions in one launch, with the nearest-
+ * neighbour indices idx_p [B][M] (into gts) and idx_g [B][N] (into preds), int32, lowest index on a tie.  The distance is
+ * the direct form dx^2 + dy^2 + dz^2 (the reference's |x|^2 + |y|^2 - 2 x.y of :19-35 cancels in fp32).  Block partials
+ * go through the workspace and are folded in fp64.  Any M, N >= 1; B <= 65535.
+ * _bwd: its gradient from g [B] and the forward's indices; dpreds or dgts may be NULL (not both).  No atomics: a lane
+ * scans the other side's index array for its own index in ascending order. */
+size_t sivae_chamfer_workspace_bytes(int B, int M, int N);
+int sivae_chamfer_fwd(const float* preds, const float* gts, int* idx_p, int* idx_g, float* loss, int B, int M, int N,
+                      void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+int sivae_chamfer_bwd(const float* g, const float* preds, const float* gts, const int* idx_p, const int* idx_g,
+                      float* dpreds, float* dgts, int B, int M, int N, sivae_stream_t stream);
+/* nn.ReLU -> nn.BatchNorm1d over a [B][C][N] (soft_intro_vae_3d/models/vae.py:105-128: the activation comes FIRST), from
+ * the conv output a; relu(a) is never stored.  _stats: mean / invstd of relu(a) per channel and the running-buffer update
+ * of sivae_bn_stats (running_mean / running_var NULL together: no update).  _apply: y = gamma (relu(a) - mean) invstd +
+ * beta (eval mode: mean / invstd from the running buffers).  _bwd: dbeta = sum dy, dgamma = sum dy rhat,
+ * da = [a > 0] gamma invstd (dy - dbeta / m - rhat dgamma / m), m = B N; ReLU's derivative at 0 is 0.  Any N >= 1;
+ * 16-byte accesses when N % 4 == 0 and the tensors are 16-byte aligned.  One workspace size serves _stats and _bwd. */
+size_t sivae_relu_bn_workspace_bytes(int B, int C, int N);
+int sivae_relu_bn_stats(const float* a, int B, int C, int N, float eps, float momentum, float* running_mean,
+                        float* running_var, long long* num_batches_tracked, float* mean_out, float* invstd_out,
+                        void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+int sivae_relu_bn_apply(const float* a, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                        float* y, int B, int C, int N, sivae_stream_t stream);
+int sivae_relu_bn_bwd(const float* dy, const float* a, const float* mean, const float* invstd, const float* gamma,
+                      float* da, float* dgamma, float* dbeta, int B, int C, int N, void* workspace, size_t workspace_bytes,
+                      sivae_stream_t stream);
+/* output.max(dim=2) (soft_intro_vae_3d/models/vae.py:141): x [B][C][N] -> vals [B][C] and the int32 argmax [B][C]
+ * (lowest index on a tie); _bwd writes g [B][C] at the argmax of an otherwise zero dx [B][C][N] in one kernel. */
+int sivae_max_points_fwd(const float* x, float* vals, int* arg, int B, int C, int N, sivae_stream_t stream);
+int sivae_max_points_bwd(const float* g, const int* arg, float* dx, int B, int C, int N, sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

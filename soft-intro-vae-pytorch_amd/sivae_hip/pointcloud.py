@@ -1,0 +1,260 @@
+"""Point-cloud building blocks of the 3-D Soft-IntroVAE (reference: soft_intro_vae_3d/), on the kernels of
+csrc/pointcloud.hip: tensor-level wrappers in the style of `ops` and the autograd Functions on top of them.
+
+  chamfer_distance(preds [B, M, 3], gts [B, N, 3]) -> [B]       losses/chamfer_loss.py:11-17 (direct-form distances)
+  relu_bn(a [B, C, N], weight, bias, BNState)      -> [B, C, N]  nn.ReLU -> nn.BatchNorm1d, relu(a) never stored
+  max_points(y [B, C, N])                          -> [B, C]     y.max(dim=2)[0]
+  pointwise_conv(x [B, Ci, N], w [Co, Ci, 1], bias, relu=False)  nn.Conv1d(kernel_size=1) on the ks = 1 conv kernels
+
+The pointwise convolutions and the MLPs run on what exists (`ops.conv2d_fwd` / `conv2d_wgrad` with ks = 1, `SF.linear`).
+There is no CPU path: a CPU tensor raises the engine's usual message.
+"""
+import torch
+
+from . import functional as SF
+from . import lib as _lib
+from . import ops
+from .ops import _p, _require, _s, timer_begin, timer_end, workspace
+
+BN_EVAL_BWD_MSG = "sivae_hip: backward through eval-mode BatchNorm is not supported"  # (the image blocks' message)
+
+
+def _require_i32(*tensors):
+    for t in tensors:
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError("sivae_hip: expected a contiguous int32 ROCm tensor")
+
+
+def _require_f32(*tensors):
+    _require(*tensors)
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("sivae_hip: expected float32, got %s" % t.dtype)
+
+
+# ------------------------------------------------------------------------------------------------ tensor level
+def chamfer_fwd(preds, gts):
+    """preds [B, M, 3], gts [B, N, 3] -> (loss [B], idx_p int32 [B, M] into gts, idx_g int32 [B, N] into preds)"""
+    _require_f32(preds, gts)
+    if preds.dim() != 3 or gts.dim() != 3 or preds.shape[2] != 3 or gts.shape[2] != 3 or preds.shape[0] != gts.shape[0]:
+        raise ValueError("sivae_hip.chamfer: expected preds [B, M, 3] and gts [B, N, 3], got %s and %s"
+                         % (tuple(preds.shape), tuple(gts.shape)))
+    B, M, N = preds.shape[0], preds.shape[1], gts.shape[1]
+    ws = workspace(_lib.load().sivae_chamfer_workspace_bytes(B, M, N), preds.device)
+    idx_p = torch.empty((B, M), dtype=torch.int32, device=preds.device)
+    idx_g = torch.empty((B, N), dtype=torch.int32, device=preds.device)
+    loss = torch.empty(B, dtype=torch.float32, device=preds.device)
+    t0 = timer_begin()
+    _lib.call("sivae_chamfer_fwd", _p(preds), _p(gts), _p(idx_p), _p(idx_g), _p(loss), B, M, N, _p(ws), ws.numel(),
+              _s(preds))
+    if t0 is not None:
+        timer_end(t0, "chamfer_fwd_kernel", 2.0 * 8 * B * M * N)
+    return loss, idx_p, idx_g
+
+
+def chamfer_bwd(g, preds, gts, idx_p, idx_g, want_dpreds=True, want_dgts=False):
+    """-> (dpreds or None, dgts or None) from the upstream gradient g [B] and the forward's indices"""
+    _require_f32(g, preds, gts)
+    _require_i32(idx_p, idx_g)
+    B, M, N = preds.shape[0], preds.shape[1], gts.shape[1]
+    if g.numel() != B or tuple(idx_p.shape) != (B, M) or tuple(idx_g.shape) != (B, N):
+        raise ValueError("sivae_hip.chamfer_bwd: g [B], idx_p [B, M], idx_g [B, N] expected")
+    if not (want_dpreds or want_dgts):
+        return None, None
+    dp = torch.empty_like(preds) if want_dpreds else None
+    dg = torch.empty_like(gts) if want_dgts else None
+    t0 = timer_begin()
+    _lib.call("sivae_chamfer_bwd", _p(g), _p(preds), _p(gts), _p(idx_p), _p(idx_g), _p(dp), _p(dg), B, M, N, _s(preds))
+    if t0 is not None:
+        timer_end(t0, "chamfer_bwd_kernel", 1.0 * B * M * N * (int(want_dpreds) + int(want_dgts)))
+    return dp, dg
+
+
+def _bcn(a):
+    if a.dim() != 3:
+        raise ValueError("sivae_hip: expected a [B, C, N] tensor, got %s" % (tuple(a.shape),))
+    return a.shape
+
+
+def relu_bn_stats(a, running_mean=None, running_var=None, num_batches_tracked=None, eps=1e-5, momentum=0.1):
+    """per-channel (mean, invstd) of relu(a), a [B, C, N]; the running buffers get sivae_bn_stats' update"""
+    _require_f32(a, running_mean, running_var)
+    _require(num_batches_tracked)
+    B, C, N = _bcn(a)
+    ws = workspace(_lib.load().sivae_relu_bn_workspace_bytes(B, C, N), a.device)
+    mean = torch.empty(C, dtype=torch.float32, device=a.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=a.device)
+    t0 = timer_begin()
+    _lib.call("sivae_relu_bn_stats", _p(a), B, C, N, float(eps), float(momentum), _p(running_mean), _p(running_var),
+              _p(num_batches_tracked), _p(mean), _p(invstd), _p(ws), ws.numel(), _s(a))
+    if t0 is not None:
+        timer_end(t0, "relu_bn_reduce_kernel", 4.0 * a.numel())
+    return mean, invstd
+
+
+def relu_bn_apply(a, mean, invstd, gamma, beta):
+    """y = gamma * (relu(a) - mean) * invstd + beta"""
+    _require_f32(a, mean, invstd, gamma, beta)
+    B, C, N = _bcn(a)
+    y = torch.empty_like(a)
+    t0 = timer_begin()
+    _lib.call("sivae_relu_bn_apply", _p(a), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(y), B, C, N, _s(a))
+    if t0 is not None:
+        timer_end(t0, "relu_bn_apply_kernel", 3.0 * a.numel())
+    return y
+
+
+def relu_bn_bwd(dy, a, mean, invstd, gamma):
+    """-> (da, dgamma, dbeta), relu(a) recomputed"""
+    _require_f32(dy, a, mean, invstd, gamma)
+    B, C, N = _bcn(a)
+    if dy.shape != a.shape:
+        raise ValueError("sivae_hip.relu_bn_bwd: dy and a differ in shape")
+    ws = workspace(_lib.load().sivae_relu_bn_workspace_bytes(B, C, N), a.device)
+    da = torch.empty_like(a)
+    dgamma = torch.empty(C, dtype=torch.float32, device=a.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=a.device)
+    t0 = timer_begin()
+    _lib.call("sivae_relu_bn_bwd", _p(dy), _p(a), _p(mean), _p(invstd), _p(gamma), _p(da), _p(dgamma), _p(dbeta), B, C, N,
+              _p(ws), ws.numel(), _s(a))
+    if t0 is not None:
+        timer_end(t0, "relu_bn_bwd", 12.0 * a.numel())
+    return da, dgamma, dbeta
+
+
+def max_points_fwd(x):
+    """x [B, C, N] -> (values [B, C], int32 argmax [B, C], lowest index on a tie)"""
+    _require_f32(x)
+    B, C, N = _bcn(x)
+    vals = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    arg = torch.empty((B, C), dtype=torch.int32, device=x.device)
+    _lib.call("sivae_max_points_fwd", _p(x), _p(vals), _p(arg), B, C, N, _s(x))
+    return vals, arg
+
+
+def max_points_bwd(g, arg, N):
+    """g [B, C] placed at arg in a zero [B, C, N] tensor"""
+    _require_f32(g)
+    _require_i32(arg)
+    B, C = g.shape
+    dx = torch.empty((B, C, N), dtype=torch.float32, device=g.device)
+    _lib.call("sivae_max_points_bwd", _p(g), _p(arg), _p(dx), B, C, N, _s(g))
+    return dx
+
+
+# ------------------------------------------------------------------------------------------------ autograd
+class ChamferFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, preds, gts):
+        # (the training loop passes x.permute(0, 2, 1) + 0.5: not contiguous)
+        preds, gts = preds.contiguous(), gts.contiguous()
+        loss, idx_p, idx_g = chamfer_fwd(preds, gts)
+        ctx.save_for_backward(preds, gts, idx_p, idx_g)
+        ctx.mark_non_differentiable(idx_p, idx_g)
+        return loss, idx_p, idx_g
+
+    @staticmethod
+    def backward(ctx, g, _gp, _gg):
+        preds, gts, idx_p, idx_g = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return chamfer_bwd(g.contiguous(), preds, gts, idx_p, idx_g, need[0], need[1])
+
+
+def chamfer_distance(preds, gts, return_indices=False):
+    """per-cloud Chamfer distance [B] (differentiable in both arguments); return_indices: also the nearest-neighbour
+    indices (idx_p [B, M] into gts, idx_g [B, N] into preds)"""
+    loss, idx_p, idx_g = ChamferFn.apply(preds, gts)
+    return (loss, idx_p, idx_g) if return_indices else loss
+
+
+class ReluBnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, weight, bias, st):
+        a = a.contiguous()
+        if st.training:
+            mean, invstd = relu_bn_stats(a, st.running_mean, st.running_var, st.num_batches_tracked, st.eps,
+                                         st.momentum if st.momentum is not None else 0.1)
+        else:
+            mean, invstd = st.running_mean, torch.rsqrt(st.running_var + st.eps)
+        ctx.training = st.training
+        ctx.save_for_backward(a, mean, invstd, weight)
+        return relu_bn_apply(a, mean, invstd, weight.detach(), bias.detach())
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.training:
+            raise RuntimeError(BN_EVAL_BWD_MSG)
+        a, mean, invstd, weight = ctx.saved_tensors
+        da, dgamma, dbeta = relu_bn_bwd(dy.contiguous(), a, mean, invstd, weight.detach())
+        return da, dgamma, dbeta, None
+
+
+def relu_bn(a, weight, bias, st):
+    """BatchNorm1d(ReLU(a)) for a [B, C, N]; st: the BatchNorm module's `functional.BNState` (buffers + mode)"""
+    return ReluBnFn.apply(a, weight, bias, st)
+
+
+class MaxPointsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y):
+        y = y.contiguous()
+        vals, arg = max_points_fwd(y)
+        ctx.save_for_backward(arg)
+        ctx.N = y.shape[2]
+        return vals
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        return max_points_bwd(g.contiguous(), arg, ctx.N)
+
+
+def max_points(y):
+    return MaxPointsFn.apply(y)
+
+
+def _pack1(w, mode):
+    """GEMM operand of a Conv1d(kernel_size=1) weight [Co, Ci, 1] through its 4-D view, cached ON the parameter under
+    functional's tag (version counter, storage): an in-place step of a stock torch.optim optimizer invalidates it"""
+    Co, Ci = w.shape[0], w.shape[1]
+    return SF._cached_pack(w, ("conv1d", mode), lambda: ops.PackedW(w.detach().view(Co, Ci, 1, 1), mode))
+
+
+class PointwiseConvFn(torch.autograd.Function):
+    """nn.Conv1d(Ci, Co, kernel_size=1) (+ ReLU) over [B, Ci, N] as the ks = 1 convolution over [B, Ci, 1, N]"""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, relu):
+        x = x.contiguous()
+        B, Ci, N = x.shape
+        Co = w.shape[0]
+        if w.dim() != 3 or w.shape[1] != Ci or w.shape[2] != 1:
+            raise RuntimeError("sivae_hip: pointwise conv expects a [Co, %d, 1] weight, got %s" % (Ci, tuple(w.shape)))
+        b_ = None if bias is None else bias.detach()
+        y = ops.conv2d_fwd(x.view(B, Ci, 1, N), _pack1(w, 0), Co, 1, bias=b_).view(B, Co, N)
+        if relu:
+            ops.relu_fwd(y, inplace=True)
+        ctx.relu = relu
+        ctx.save_for_backward(x, w, y if relu else None, bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y, bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy = dy.contiguous()
+        if ctx.relu:
+            dy = ops.relu_bwd(dy, y)
+        B, Ci, N = x.shape
+        Co = w.shape[0]
+        dy4 = dy.view(B, Co, 1, N)
+        dw = ops.conv2d_wgrad(x.view(B, Ci, 1, N), dy4, 1).view(Co, Ci, 1) if need[1] else None
+        db = ops.channel_sum(dy4) if (bias is not None and need[2]) else None
+        dx = ops.conv2d_fwd(dy4, _pack1(w, 1), Ci, 1).view(B, Ci, N) if need[0] else None
+        return dx, dw, db, None
+
+
+def pointwise_conv(x, w, bias=None, relu=False):
+    return PointwiseConvFn.apply(x, w, bias, relu)
