@@ -717,6 +717,32 @@ int sivae_relu_bn_bwd(const float* dy, const float* a, const float* mean, const 
 int sivae_max_points_fwd(const float* x, float* vals, int* arg, int B, int C, int N, sivae_stream_t stream);
 int sivae_max_points_bwd(const float* g, const int* arg, float* dx, int B, int C, int N, sivae_stream_t stream);
 
+/* ---- point clouds: the JSD validation metric (pc_jsd.hip) ----------------------------------------------------------
+ * _entropy_of_occupancy_grid (soft_intro_vae_3d/metrics/jsd.py:97-126, the NearestNeighbors fit and the per-point Python
+ * loop): S clouds of N points, read in place through three ELEMENT strides (cloud, point, coordinate), against the table
+ * of grid-cell centres cells [G][3] in the reference's order (row-major over (i, j, k), cells outside the sphere dropped
+ * when clipping is on, _unit_cube_grid_point_cloud :139-157).  counters[c] = points whose nearest centre is c,
+ * bernoulli[c] = clouds with at least one such point (may be NULL); both int32 [G], zeroed here.  lut [res^3] maps a cell
+ * of the full cube to its table index (-1: dropped), axis [res] holds the float32 centre coordinates of one axis.
+ * A point whose own cube cell is in the table takes that cell; any other point is compared with EVERY table entry
+ * (direct-form float32 distances, lowest index on a tie).  status [2] (zeroed here): [0] points with a non-finite
+ * coordinate (skipped), [1] points that took the exhaustive comparison.  2 <= res <= 64; SIVAE_ERR_RANGE for
+ * S N >= 2^31.  Integer atomics only: two runs are bit-identical. */
+int sivae_occupancy_grid(const float* pcs, long long stride_s, long long stride_n, long long stride_c, int S, int N,
+                         const float* cells, const int* lut, const float* axis, int res, int G, int* counters,
+                         int* bernoulli, int* status, sivae_stream_t stream);
+/* _pc_to_voxel_distribution (metrics/jsd.py:63-72): counts [n_voxels^3] int32 (zeroed here) of
+ * int((clamp(x, -0.5, 0.4999) + 0.5) * n_voxels) per coordinate, linear index (ix n + iy) n + iz, in the reference's
+ * float32 operations (separately rounded add and multiply).  status [1] (zeroed here): points with a NaN coordinate
+ * (skipped).  The same three element strides as above. */
+int sivae_voxel_histogram(const float* pc, long long stride_s, long long stride_n, long long stride_c, int S, int N,
+                          int n_voxels, int* counts, int* status, sivae_stream_t stream);
+/* _js_divergence (metrics/jsd.py:25-42) of two count vectors of n entries, int32 (flag 0) or float64 (flag 1): both are
+ * normalised, out[0] = H((P + Q) / 2) - (H(P) + H(Q)) / 2 with base-2 entropies and 0 log 0 = 0, in float64, one block,
+ * fixed reduction order.  A zero total gives NaN, as the reference's 0 / 0 does. */
+int sivae_js_divergence(const void* P, const void* Q, int p_is_f64, int q_is_f64, int n, double* out,
+                        sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

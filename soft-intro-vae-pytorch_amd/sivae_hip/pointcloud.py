@@ -6,9 +6,16 @@ csrc/pointcloud.hip: tensor-level wrappers in the style of `ops` and the autogra
   max_points(y [B, C, N])                          -> [B, C]     y.max(dim=2)[0]
   pointwise_conv(x [B, Ci, N], w [Co, Ci, 1], bias, relu=False)  nn.Conv1d(kernel_size=1) on the ks = 1 conv kernels
 
+and the validation metric (metrics/jsd.py) on the kernels of csrc/pc_jsd.hip, not differentiable:
+
+  occupancy_grid(pcs [S, N, 3], resolution, in_sphere=False) -> (counters, bernoulli) int32 [G]
+  voxel_histogram(pc [S, N, 3], n_voxels)                    -> counts int32 [n_voxels^3]
+  js_divergence(P, Q)                                        -> 0-dim float64 tensor
+
 The pointwise convolutions and the MLPs run on what exists (`ops.conv2d_fwd` / `conv2d_wgrad` with ks = 1, `SF.linear`).
 There is no CPU path: a CPU tensor raises the engine's usual message.
 """
+import numpy as np
 import torch
 
 from . import functional as SF
@@ -142,6 +149,125 @@ def max_points_bwd(g, arg, N):
     dx = torch.empty((B, C, N), dtype=torch.float32, device=g.device)
     _lib.call("sivae_max_points_bwd", _p(g), _p(arg), _p(dx), B, C, N, _s(g))
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ the JSD metric
+def unit_cube_grid(resolution, clip_sphere=False):
+    """host float32 table of the reference's _unit_cube_grid_point_cloud (metrics/jsd.py:139-157)
+    -> (axis [res], mask [res^3] bool in row-major (i, j, k) order, spacing): the centre of cell (i, j, k) is
+    (axis[i], axis[j], axis[k]) with axis[i] = float32(i * spacing - 0.5); mask keeps a cell where the float32 norm of its
+    centre is <= 0.5 (all of them without clipping)"""
+    resolution = int(resolution)
+    if resolution < 2:
+        raise ValueError("sivae_hip.occupancy_grid: resolution must be at least 2, got %d" % resolution)
+    spacing = 1.0 / float(resolution - 1)
+    axis = (np.arange(resolution, dtype=np.float64) * spacing - 0.5).astype(np.float32)
+    if clip_sphere:
+        sq = axis * axis  # (numpy.linalg.norm over the last axis: sqrt of the float32 sum of squares, in axis order)
+        nrm = np.sqrt((sq[:, None, None] + sq[None, :, None]) + sq[None, None, :])
+        mask = (nrm <= np.float32(0.5)).reshape(-1)
+    else:
+        mask = np.ones(resolution ** 3, dtype=bool)
+    return axis, mask, spacing
+
+
+def grid_cells(axis, mask):
+    """-> the table of centres [G, 3] float32 in the reference's order"""
+    r = len(axis)
+    full = np.stack(np.meshgrid(axis, axis, axis, indexing="ij"), axis=-1).reshape(r ** 3, 3)
+    return np.ascontiguousarray(full[mask])
+
+
+_grids = {}
+
+
+def device_grid(device, resolution, in_sphere=False):
+    """(cells [G, 3], lut int32 [res^3], axis [res]) on the device, cached per (device, resolution, in_sphere)"""
+    key = (device.index, int(resolution), bool(in_sphere))
+    g = _grids.get(key)
+    if g is None:
+        axis, mask, _ = unit_cube_grid(resolution, in_sphere)
+        lut = np.full(mask.shape[0], -1, dtype=np.int32)
+        lut[mask] = np.arange(int(mask.sum()), dtype=np.int32)
+        g = tuple(torch.from_numpy(a).to(device) for a in (grid_cells(axis, mask), lut, axis))
+        _grids[key] = g
+    return g
+
+
+def _require_clouds(pcs, who):
+    """[S, N, 3] float32 on a ROCm device, ANY strides (read in place) -> (S, N, element strides)"""
+    if not pcs.is_cuda:
+        _require(pcs)  # (the engine's message)
+    if pcs.dtype != torch.float32:
+        raise TypeError("sivae_hip: expected float32, got %s" % pcs.dtype)
+    if pcs.dim() != 3 or pcs.shape[2] != 3 or pcs.shape[0] == 0 or pcs.shape[1] == 0:
+        raise ValueError("sivae_hip.%s: expected point clouds [S, N, 3], got %s" % (who, tuple(pcs.shape)))
+    return pcs.shape[0], pcs.shape[1], pcs.stride()
+
+
+def occupancy_grid(pcs, resolution, in_sphere=False, want_bernoulli=True, return_status=False):
+    """_entropy_of_occupancy_grid's counting (metrics/jsd.py:113-126): -> (counters, bernoulli), int32 [G] each, over the
+    resolution^3 cells (the ones inside the sphere when in_sphere); bernoulli is None when not wanted.  return_status:
+    also the int32 [2] device word pair (non-finite points, points on the exhaustive route).  A non-finite coordinate
+    raises ValueError (what sklearn's input check does in the reference)."""
+    S, N, st = _require_clouds(pcs, "occupancy_grid")
+    cells, lut, axis = device_grid(pcs.device, resolution, in_sphere)
+    G = cells.shape[0]
+    counters = torch.empty(G, dtype=torch.int32, device=pcs.device)
+    bernoulli = torch.empty(G, dtype=torch.int32, device=pcs.device) if want_bernoulli else None
+    status = torch.empty(2, dtype=torch.int32, device=pcs.device)
+    t0 = timer_begin()
+    _lib.call("sivae_occupancy_grid", _p(pcs), st[0], st[1], st[2], S, N, _p(cells), _p(lut), _p(axis), int(resolution), G,
+              _p(counters), _p(bernoulli), _p(status), _s(pcs))
+    t1 = ops.TIMER.begin() if t0 is not None else None  # (the end event, right behind the launch)
+    bad, exhaustive = status.tolist()  # (one read; it synchronises, which a metric may)
+    if t0 is not None:
+        # 8 operations per distance of the exhaustive route, about 30 per point for the lookup route and the counting;
+        # the record is appended here because the work is only known once the status words are back
+        work = 8.0 * exhaustive * G + 30.0 * S * N
+        ops.TIMER.records.append(("occupancy_grid_kernel", work, t0, t1, work))
+    if bad:
+        raise ValueError("sivae_hip.occupancy_grid: %d point(s) with a NaN or infinite coordinate" % bad)
+    return (counters, bernoulli, status) if return_status else (counters, bernoulli)
+
+
+def voxel_histogram(pc, n_voxels):
+    """_pc_to_voxel_distribution (metrics/jsd.py:63-72) -> counts int32 [n_voxels^3]"""
+    S, N, st = _require_clouds(pc, "voxel_histogram")
+    n_voxels = int(n_voxels)
+    if n_voxels < 1:
+        raise ValueError("sivae_hip.voxel_histogram: n_voxels must be positive")
+    counts = torch.empty(n_voxels ** 3, dtype=torch.int32, device=pc.device)
+    status = torch.empty(1, dtype=torch.int32, device=pc.device)
+    t0 = timer_begin()
+    _lib.call("sivae_voxel_histogram", _p(pc), st[0], st[1], st[2], S, N, n_voxels, _p(counts), _p(status), _s(pc))
+    if t0 is not None:
+        timer_end(t0, "voxel_histogram_kernel", 9.0 * S * N)
+    bad = int(status[0])
+    if bad:
+        raise ValueError("sivae_hip.voxel_histogram: %d point(s) with a NaN coordinate" % bad)
+    return counts
+
+
+def js_divergence(P, Q):
+    """_js_divergence (metrics/jsd.py:25-42) of two count vectors (int32 or float64, equal length) -> 0-dim float64"""
+    for t in (P, Q):
+        if not t.is_cuda:
+            _require(t)
+        if t.dtype not in (torch.int32, torch.float64) or not t.is_contiguous():
+            raise TypeError("sivae_hip.js_divergence: expected contiguous int32 or float64 counts, got %s" % t.dtype)
+    if P.device != Q.device:
+        raise ValueError("sivae_hip.js_divergence: P is on %s, Q on %s" % (P.device, Q.device))
+    if P.dim() != 1 or P.shape != Q.shape or P.numel() == 0:
+        raise ValueError("sivae_hip.js_divergence: two vectors of equal length expected, got %s and %s"
+                         % (tuple(P.shape), tuple(Q.shape)))
+    out = torch.empty((), dtype=torch.float64, device=P.device)
+    t0 = timer_begin()
+    _lib.call("sivae_js_divergence", _p(P), _p(Q), int(P.dtype == torch.float64), int(Q.dtype == torch.float64), P.numel(),
+              _p(out), _s(P))
+    if t0 is not None:
+        timer_end(t0, "js_divergence_kernel", 12.0 * P.numel())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ autograd
