@@ -198,7 +198,9 @@ static RbPlan rb_plan(long long n, int C) {
   return p;
 }
 
-__device__ __forceinline__ float relu0(float v) { return v > 0.f ? v : 0.f; }  // (derivative at 0 is 0: `>` everywhere)
+// relu with torch's NaN rule: a NaN activation stays a NaN (`v > 0 ? v : 0` would turn it into 0 and hide a diverged run
+// behind finite statistics).  The derivative at 0 is 0: the backward's gate is `a > 0`.
+__device__ __forceinline__ float relu0(float v) { return v <= 0.f ? 0.f : v; }
 
 // BWD = false: (sum r, sum r^2) of r = relu(a);  BWD = true: (sum dy, sum dy * r)
 template <bool VEC, bool BWD>
@@ -414,8 +416,20 @@ extern "C" int sivae_relu_bn_bwd(const float* dy, const float* a, const float* m
 // ------------------------------------------------------------------------------------------------ max over points
 // One wave per [b][c] row: lanes walk the row (16-byte loads when N % 4 == 0) keeping (value, lowest index), then a
 // butterfly on the pair.  The lowest index wins a tie, inside a lane (ascending walk, strict compare) and across lanes.
+// A NaN is the maximum, as in torch.max: it beats every number, and among NaNs the lowest index wins — the same rule
+// inside a lane and in the butterfly.  `!(v <= bv)` holds where v is greater or either side is a NaN; v then wins unless
+// the NaN is bv's alone.
 __device__ __forceinline__ void max_take(float& bv, int& bi, float v, int i) {
-  if (v > bv || (v == bv && i < bi)) {
+  if (!(v <= bv) ? (bv == bv || (v != v && i < bi)) : (v == bv && i < bi)) {
+    bv = v;
+    bi = i;
+  }
+}
+// max_take for a lane's ascending walk (i above every index taken so far): an equal value or a second NaN never takes
+// over, so two compares decide — and the loop-carried chain compare -> select is no longer than a plain maximum's.
+// (A lane that saw -inf only keeps the start index 0x7fffffff: -inf at a real index of another lane wins the tie.)
+__device__ __forceinline__ void max_walk(float& bv, int& bi, float v, int i) {
+  if (!(v <= bv) && bv == bv) {
     bv = v;
     bi = i;
   }
@@ -432,13 +446,13 @@ __global__ void __launch_bounds__(PC_NT) max_points_fwd_kernel(const float* __re
   if (VEC) {
     for (int i = lane * 4; i < N; i += 256) {
       const float4 v = *reinterpret_cast<const float4*>(p + i);
-      max_take(bv, bi, v.x, i);
-      max_take(bv, bi, v.y, i + 1);
-      max_take(bv, bi, v.z, i + 2);
-      max_take(bv, bi, v.w, i + 3);
+      max_walk(bv, bi, v.x, i);
+      max_walk(bv, bi, v.y, i + 1);
+      max_walk(bv, bi, v.z, i + 2);
+      max_walk(bv, bi, v.w, i + 3);
     }
   } else {
-    for (int i = lane; i < N; i += 64) max_take(bv, bi, p[i], i);
+    for (int i = lane; i < N; i += 64) max_walk(bv, bi, p[i], i);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -448,7 +462,7 @@ __global__ void __launch_bounds__(PC_NT) max_points_fwd_kernel(const float* __re
   }
   if (lane == 0) {
     vals[row] = bv;
-    arg[row] = bi < N ? bi : 0;  // (a row of NaNs / -inf only: index 0)
+    arg[row] = bi < N ? bi : 0;  // (a row of -inf only: no lane took an element; index 0)
   }
 }
 

@@ -202,6 +202,11 @@ def vae_objective(sd, x, eps, beta_rec=20.0, beta_kl=1.0, training=True, update=
     return dict(mu=mu, logvar=logvar, rec=rec, chamfer=ch, kl=k, loss=beta_rec * ch.mean() + beta_kl * k)
 
 
+# [B, C, N] -> number of slices a channel's B * N values are cut into by the ReLU -> BatchNorm kernels: the shapes of
+# tests/test_pointcloud_paths_gpu.py::test_relu_bn_sliced, pinned on the host by test_pointcloud_host.py
+RELU_BN_SLICED = {(3, 5, 1368): 2, (3, 7, 2731): 3, (9, 3, 1001): 3, (4, 1024, 2052): 2, (32, 64, 2048): 16}
+
+
 def rel_l2(a, b):
     """|a - b|_2 / |b|_2 in fp64"""
     a, b = a.detach().double().cpu().reshape(-1), b.detach().double().cpu().reshape(-1)

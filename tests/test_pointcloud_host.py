@@ -188,6 +188,28 @@ def test_pointcloud_entry_points_validate_arguments():
     assert mb(one, null, one, 2, 4, 8, null) == -1 and mb(one, one, one, 0, 4, 8, null) == -2
 
 
+def test_relu_bn_slice_counts():
+    """sivae_relu_bn_workspace_bytes(B, C, N) = C * S * 16 tells the number S of slices a channel's B * N values are cut
+    into.  The shapes of tests/test_pointcloud_paths_gpu.py::test_relu_bn_sliced must give S > 1 (the S of the issue's
+    table), the four shapes of tests/test_pointcloud_gpu.py::test_relu_bn give S = 1: if the slicing policy changes, this
+    says that the GPU cases no longer reach the multi-slice reduction"""
+    L = lib.load()
+    sliced = O.RELU_BN_SLICED
+    assert sorted(sliced.values()) == [2, 2, 3, 3, 16]
+    single = [(3, 64, 100), (2, 512, 2048), (4, 5, 1), (1, 7, 33)]
+    got = {}
+    for B, C, N in list(sliced) + single:
+        nbytes = L.sivae_relu_bn_workspace_bytes(B, C, N)
+        assert nbytes > 0 and nbytes % (C * 16) == 0, (B, C, N, nbytes)
+        got[(B, C, N)] = nbytes // (C * 16)
+    assert got == {**sliced, **{k: 1 for k in single}}, got
+    assert L.sivae_relu_bn_workspace_bytes(32, 512, 2048) == 512 * 4 * 16  # (the training shape of the last stage)
+    # the seam case's slice length is 3072: ceil(B N / S) rounded up to 1024
+    for B, C, N in [(3, 5, 1368), (3, 7, 2731)]:
+        S = sliced[(B, C, N)]
+        assert ((B * N + S - 1) // S + 1023) // 1024 * 1024 == 3072
+
+
 def test_build_imports_the_pointcloud_modules():
     import __graft_entry__ as G
     src = inspect.getsource(G.build)
