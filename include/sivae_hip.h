@@ -68,7 +68,7 @@ int sivae_pack_batch(int form, const void* jobs_dev, const unsigned short* block
  *        pro_mean != NULL (producer BatchNorm2d + LeakyReLU fused into the load, :58-59,:90-91);
  *   upsample != 0: x is [B][Ci][H/2][W/2] and is read through nn.Upsample(2,'nearest') (:155);
  *   stats_partial != NULL: per-pixel-tile per-channel {sum, sumsq} of y, [n_px_tiles][Co][2], for the
- *        consumer BatchNorm2d (see sivae_bn_stats_from_conv);
+ *        consumer BatchNorm2d (see sivae_bn_stats_from_conv_ws);
  *   accumulate != 0: y += result (used to sum the two branches of the residual data gradient).
  * The data gradient of the same conv is this function on dy with the mode-1 pack (Ci/Co swapped):
  * aten::convolution_backward (input half). */
@@ -222,14 +222,13 @@ int sivae_conv5_edge_wgrad(const float* x, const float* dy, float* dw, int B, in
 
 /* ---- BatchNorm2d (training mode) + LeakyReLU + residual add ----------------------------------------
  * nn.BatchNorm2d(eps 1e-5, momentum 0.1) :58,:62,:90 ; nn.LeakyReLU(0.2) :59,:63,:91 ; torch.add :74.
- * running_var gets the unbiased variance, num_batches_tracked (int64, device) is incremented. */
+ * running_var gets the unbiased variance, num_batches_tracked (int64, device) is incremented.  Statistics from the conv
+ * epilogue's partials, the running-buffer replay, the apply pass and the backward take `seg_images` / `nseg` and are
+ * declared under "segmented batches" below: one segment (seg_images == B, nseg = 1) is the unsegmented op. */
 size_t sivae_bn_workspace_bytes(int B, int C, int HW);
 int sivae_bn_stats(const float* x, int B, int C, int HW, float eps, float momentum, float* running_mean,
                    float* running_var, long long* num_batches_tracked, float* mean_out, float* invstd_out,
                    void* workspace, size_t workspace_bytes, sivae_stream_t stream);
-int sivae_bn_stats_from_conv(const float* partials, int n_tiles, int B, int C, int HW, float eps, float momentum,
-                             float* running_mean, float* running_var, long long* num_batches_tracked,
-                             float* mean_out, float* invstd_out, sivae_stream_t stream);
 /* ---- synchronised BatchNorm for data-parallel runs (opt-in): the shard's per-channel {sum, sumsq}
  * (fp64 [C][2]) from the conv-epilogue partials — the caller all-reduces it — and the finalize from the (global) sums
  * and the global element count.  Backward: `reduce` leaves the local {sum dz, sum dz*xhat} (fp64 [C][2]), `apply`
@@ -246,62 +245,6 @@ int sivae_bn_bwd_apply(const float* dy, const float* y, const float* x, const fl
                        const double* sums_global, double count_global, float* dx, float* dz_out, float* dgamma,
                        float* dbeta, int B, int C, int HW, void* workspace, size_t workspace_bytes,
                        sivae_stream_t stream);
-/* one more running-stat update from saved batch statistics (a forward pass replayed from cached
- * activations still counts as one BatchNorm call of the reference); count = B*H*W. */
-int sivae_bn_update_running(const float* mean, const float* invstd, int C, double count, float eps, float momentum,
-                            float* running_mean, float* running_var, long long* num_batches_tracked,
-                            sivae_stream_t stream);
-/* y = LeakyReLU((x-mean[c])*invstd[c]*gamma[c]+beta[c] (+ res), slope); slope = 1 -> identity act. */
-int sivae_bn_apply_act(const float* x, const float* res, const float* mean, const float* invstd,
-                       const float* gamma, const float* beta, float slope, float* y, int B, int C, int HW,
-                       sivae_stream_t stream);
-/* same op, also writing AvgPool2d(2) (:92,:98) of the result in the same pass: y [B][C][H][W] (kept for backward)
- * and y_pooled [B][C][H/2][W/2]; res may be NULL; y may be NULL (pooled output only: the stem, whose backward
- * recomputes the activation from the conv output); H even, W % 4 == 0. */
-int sivae_bn_apply_act_pool(const float* x, const float* res, const float* mean, const float* invstd,
-                            const float* gamma, const float* beta, float slope, float* y, float* y_pooled, int B, int C,
-                            int H, int W, sivae_stream_t stream);
-/* same, with the residual stored at half resolution [B][C][H/2][W/2] and read through nn.Upsample(2,'nearest')
- * (:155) addressing — the upsampled tensor is never written; H even, W % 4 == 0. */
-int sivae_bn_apply_act_resup(const float* x, const float* res_half, const float* mean, const float* invstd,
-                             const float* gamma, const float* beta, float slope, float* y, int B, int C, int H, int W,
-                             sivae_stream_t stream);
-/* LeakyReLU sign mask (1 bit per element: pre-activation > 0; element e -> bit e&7 of byte e>>3).  The apply pass
- * of "LeakyReLU(BN(x) + res)" (ResidualBlock output, train_soft_intro_vae.py:71-74) writes it next to its output and
- * the backward reads it instead of the saved output: 1/32 of a tensor per backward pass, and an encoder block
- * (output consumed only through the AvgPool2d behind it, :95-99) never writes its full-resolution output.
- *   y_pooled != NULL: + AvgPool2d(2), y may be NULL; res_up != 0: res is [B][C][H/2][W/2] read through
- *   Upsample(2,'nearest') addressing (:155).  mask: sivae_bn_signmask_bytes() bytes.  H even, W % 8 == 0. */
-size_t sivae_bn_signmask_bytes(int B, int C, int HW);
-int sivae_bn_apply_act_signmask(const float* x, const float* res, int res_up, const float* mean, const float* invstd,
-                                const float* gamma, const float* beta, float slope, float* y, float* y_pooled,
-                                unsigned char* mask, int B, int C, int H, int W, sivae_stream_t stream);
-/* backward with the sign from that mask.  dy_pooled != 0: dy is the gradient of AvgPool2d(2)(output) at half
- * resolution; dz_sum != 0: dz_out = 2x2 block sums of the residual-branch gradient [B][C][H/2][W/2] (not both). */
-int sivae_bn_bwd_signmask(const float* dy, const unsigned char* mask, const float* x, const float* mean,
-                          const float* invstd, const float* gamma, float slope, float* dx, float* dz_out,
-                          float* dgamma, float* dbeta, int B, int C, int H, int W, int dy_pooled, int dz_sum,
-                          void* workspace, size_t workspace_bytes, sivae_stream_t stream);
-/* backward of the above: dz = dy*(s>0?1:slope); dx = BN backward of dz; dz_out (optional) = gradient
- * of the residual branch; dgamma/dbeta optional.  act_mode selects where the LeakyReLU sign s comes from:
- *   0 no activation, 1 the saved OUTPUT y (valid since slope > 0), 2 recomputed from x (needs beta; used
- *   when the BatchNorm output was never stored because it was fused into the next conv's load). */
-int sivae_bn_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
-                 const float* gamma, const float* beta, int act_mode, float slope, float* dx, float* dz_out,
-                 float* dgamma, float* dbeta, int B, int C, int HW, void* workspace, size_t workspace_bytes,
-                 sivae_stream_t stream);
-/* act_mode-1 backward (LeakyReLU sign from the saved output y) that returns the residual-branch gradient as its 2x2
- * block sum dz_half [B][C][H/2][W/2] — the adjoint of the nn.Upsample (:155) in front of a decoder block — instead of
- * the full-resolution dz; H even, W % 4 == 0. */
-int sivae_bn_bwd_dzsum(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
-                       const float* gamma, float slope, float* dx, float* dz_half, float* dgamma, float* dbeta, int B,
-                       int C, int H, int W, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
-/* same with dy given as the gradient of AvgPool2d(2)(y) at half resolution [B][C][H/2][W/2] (:92,:98): the pool's
- * adjoint (0.25 * dy_half[h>>1][w>>1]) is applied on load; H even, W % 4 == 0. */
-int sivae_bn_bwd_pooled_dy(const float* dy_half, const float* y, const float* x, const float* mean,
-                           const float* invstd, const float* gamma, const float* beta, int act_mode, float slope,
-                           float* dx, float* dz_out, float* dgamma, float* dbeta, int B, int C, int H, int W,
-                           void* workspace, size_t workspace_bytes, sivae_stream_t stream);
 /* out[c] = sum over (B, HW) — bias gradient of Decoder.predict (:159). Workspace as sivae_bn_workspace_bytes. */
 int sivae_channel_sum(const float* x, float* out, int B, int C, int HW, void* workspace, size_t workspace_bytes,
                       sivae_stream_t stream);
@@ -441,7 +384,7 @@ int sivae_bf16_pack_conv_weight(const float* w, void* wp, int Co, int Ci, int ks
 /* y (+)= conv(x', wp) + bias with the fusions of sivae_conv2d_fwd (producer BatchNorm+LeakyReLU prologue — 3x3 only —,
  * upsample addressing, {sum, sumsq} partials of the rounded output, accumulate).  out_f32_nchw != 0: y is float
  * [B][Co][H][W] (Co <= 32, no stats: Decoder.predict :159).  stats_partial has sivae_bf16_conv2d_num_px_tiles(B, Co, H, W, ks) rows and
- * feeds sivae_bn_stats_from_conv unchanged.  The data gradient is this function on dy with the mode-1 pack. */
+ * feeds sivae_bn_stats_from_conv_ws unchanged.  The data gradient is this function on dy with the mode-1 pack. */
 int sivae_bf16_conv2d_num_px_tiles(int B, int Co, int H, int W, int ks);
 int sivae_bf16_conv2d_fwd(const void* x, const void* wp, void* y, const float* bias, const float* pro_mean,
                           const float* pro_invstd, const float* pro_gamma, const float* pro_beta, float pro_slope,
@@ -524,13 +467,17 @@ int sivae_bf16_add_inplace(void* y, const void* x, size_t nvec, sivae_stream_t s
  * decode(z_fake) :607-608, bootstrap decode_target x2 soft_intro_vae_bootstrap/train_soft_intro_vae_bootstrap.py:635-636.
  * The engine lays such passes end to end in ONE batch of B = nseg * seg_images images ("segments", pass g = images
  * [g*seg_images, (g+1)*seg_images)).  Convolutions do not care; training-mode nn.BatchNorm2d (:58,:62,:90) must keep
- * ONE set of batch statistics PER PASS, so every BatchNorm kernel and every fused BatchNorm prologue has a _seg form:
- * mean / invstd are [nseg][C], gamma / beta / running buffers [C]; dgamma / dbeta are summed over the passes; the
- * running buffers receive one momentum update per pass in pass order.  nseg = 1 is the unsegmented op bit for bit. */
+ * ONE set of batch statistics PER PASS, so the BatchNorm entry points below take `seg_images` (or `nseg`) and every fused
+ * BatchNorm prologue has a _seg form: mean / invstd are [nseg][C], gamma / beta / running buffers [C]; dgamma / dbeta are
+ * summed over the passes; the running buffers receive one momentum update per pass in pass order.  seg_images == B
+ * (nseg = 1) is the unsegmented op, bit for bit: there is no other fp32 entry point for it. */
+/* statistics from the conv epilogue's partials ([n_tiles][C][2] rows in image order, n_tiles % nseg == 0), one-stage */
 int sivae_bn_stats_from_conv_seg(const float* partials, int n_tiles, int nseg, int seg_rev, int B_seg, int C, int HW,
                                  float eps, float momentum, float* running_mean, float* running_var,
                                  long long* num_batches_tracked, float* mean_out, float* invstd_out,
                                  sivae_stream_t stream);
+/* one more running-stat update per pass from saved batch statistics (a forward pass replayed from cached
+ * activations still counts as one BatchNorm call of the reference); count = seg_images*H*W; seg_rev: last pass first. */
 int sivae_bn_update_running_seg(const float* mean, const float* invstd, int nseg, int seg_rev, int C, double count,
                                 float eps, float momentum, float* running_mean, float* running_var,
                                 long long* num_batches_tracked, sivae_stream_t stream);
@@ -543,15 +490,36 @@ int sivae_bn_stats_from_conv_ws(const float* partials, int n_tiles, int nseg, in
                                 float eps, float momentum, float* running_mean, float* running_var,
                                 long long* num_batches_tracked, float* mean_out, float* invstd_out, void* workspace,
                                 size_t workspace_bytes, sivae_stream_t stream);
+/* y = LeakyReLU((x-mean[c])*invstd[c]*gamma[c]+beta[c] (+ res), slope); slope = 1 -> identity act; res may be NULL.
+ *   y_pooled != NULL: also writes AvgPool2d(2) (:92,:98) of the result in the same pass: y [B][C][H][W] (kept for
+ *     backward) and y_pooled [B][C][H/2][W/2]; y may be NULL with y_pooled (pooled output only: the stem, whose backward
+ *     recomputes the activation from the conv output); H even, W % 4 == 0; not with res_up.
+ *   res_up != 0: res is stored at half resolution [B][C][H/2][W/2] and read through nn.Upsample(2,'nearest') (:155)
+ *     addressing — the upsampled tensor is never written; H even, W % 4 == 0.
+ *   otherwise H and W count only as H * W (a [B][C] input goes as H = 1, W = 1). */
 int sivae_bn_apply_act_seg(const float* x, const float* res, int res_up, const float* mean, const float* invstd,
                            const float* gamma, const float* beta, float slope, float* y, float* y_pooled, int B, int C,
                            int H, int W, int seg_images, sivae_stream_t stream);
+/* The same op with the LeakyReLU sign mask as an extra output (1 bit per element: pre-activation > 0; element e -> bit
+ * e&7 of byte e>>3).  The apply pass of "LeakyReLU(BN(x) + res)" (ResidualBlock output, train_soft_intro_vae.py:71-74)
+ * writes it next to its output and the backward reads it instead of the saved output: 1/32 of a tensor per backward pass,
+ * and an encoder block (output consumed only through the AvgPool2d behind it, :95-99) never writes its full-resolution
+ * output.  y_pooled, res_up as above.  mask: sivae_bn_signmask_bytes() bytes.  H even, W % 8 == 0. */
+size_t sivae_bn_signmask_bytes(int B, int C, int HW);
 int sivae_bn_apply_act_signmask_seg(const float* x, const float* res, int res_up, const float* mean,
                                     const float* invstd, const float* gamma, const float* beta, float slope, float* y,
                                     float* y_pooled, unsigned char* mask, int B, int C, int H, int W, int seg_images,
                                     sivae_stream_t stream);
-/* every backward variant in one entry: act_mode 0 none / 1 sign from y / 2 recomputed from x (beta) / 3 from mask;
- * dy_pooled, dz_sum as in sivae_bn_bwd_signmask; workspace: sivae_bn_workspace_bytes(seg_images, nseg * C, H * W).
+/* backward of the above, every variant in one entry: dz = dy*(s>0?1:slope); dx = BN backward of dz; dz_out (optional) =
+ * gradient of the residual branch; dgamma/dbeta optional.  act_mode selects where the LeakyReLU sign s comes from:
+ *   0 no activation, 1 the saved OUTPUT y (valid since slope > 0), 2 recomputed from x (needs beta; used when the
+ *   BatchNorm output was never stored because it was fused into the next conv's load), 3 the sign mask the apply pass
+ *   wrote (y may be NULL; H even, W % 8 == 0).
+ * dy_pooled != 0: dy is the gradient of AvgPool2d(2)(output) at half resolution [B][C][H/2][W/2] (:92,:98); the pool's
+ *   adjoint (0.25 * dy_half[h>>1][w>>1]) is applied on load.  dz_sum != 0 (act_mode 1 or 3): dz_out = 2x2 block sums of the
+ *   residual-branch gradient [B][C][H/2][W/2] — the adjoint of the nn.Upsample (:155) in front of a decoder block —
+ *   instead of the full-resolution dz.  Either: H even, W % 4 == 0; not both.  Without them H and W count only as H * W.
+ * workspace: sivae_bn_workspace_bytes(seg_images, nseg * C, H * W).
  * counters: NULL, or >= C zero-initialised unsigned ints the call leaves zero (caller-owned, one stream at a time): the
  * per-channel finalize then runs inside the reduction kernel instead of as its own launch — same fixed summation order */
 int sivae_bn_bwd_seg(const float* dy, const float* y, const unsigned char* mask, const float* x, const float* mean,
@@ -607,7 +575,7 @@ int sivae_conv2d_wino_wgrad_seg(const float* x, const float* dy, float* dw, cons
  * 36 multiplies per 4x4 output tile: 1.78x fewer matrix-pipe passes than F(2x2,3x3) (sivae_conv2d_wino_fwd) at 1.2e-5
  * relative error per layer in fp32 (3.3e-5 on the reconstruction of the six-level network end to end).  Maps: H % 16 == 0,
  * W % 32 == 0.  up: [6][Ci_pad][Co_pad][6] from sivae_pack_wino4_weight (mode 0 forward, 1 data gradient).
- * stats_partial: [sivae_conv2d_wino4_num_px_tiles][Co][2] rows in image order (sivae_bn_stats_from_conv[_seg]). */
+ * stats_partial: [sivae_conv2d_wino4_num_px_tiles][Co][2] rows in image order (sivae_bn_stats_from_conv_ws / _seg). */
 size_t sivae_pack_wino4_weight_bytes(int Co, int Ci, int mode);
 int sivae_pack_wino4_weight(const float* w, float* up, int Co, int Ci, int mode, sivae_stream_t stream);
 int sivae_conv2d_wino4_supported(int H, int W); /* 1: H % 16 == 0, W % 32 == 0; 2 / 3 / 4: 16 x 16 / 8 x 8 / 4 x 4 maps — a

@@ -317,14 +317,6 @@ extern "C" int sivae_bn_stats_from_conv_ws(const float* partials, int n_tiles, i
   return sivae_launch_status();
 }
 
-extern "C" int sivae_bn_stats_from_conv(const float* partials, int n_tiles, int B, int C, int HW, float eps,
-                                        float momentum, float* running_mean, float* running_var,
-                                        long long* num_batches_tracked, float* mean_out, float* invstd_out,
-                                        hipStream_t stream) {
-  return bn_stats_from_conv_impl(partials, n_tiles, 1, 0, B, C, HW, eps, momentum, running_mean, running_var,
-                                 num_batches_tracked, mean_out, invstd_out, stream);
-}
-
 // Segmented form: the batch is `nseg` passes of `B_seg` images each (n_tiles rows in pass order, n_tiles % nseg == 0);
 // mean_out / invstd_out are [nseg][C]; the running buffers get one update per pass (seg_rev: last pass first).
 extern "C" int sivae_bn_stats_from_conv_seg(const float* partials, int n_tiles, int nseg, int seg_rev, int B_seg, int C,
@@ -397,22 +389,7 @@ extern "C" int sivae_bn_finalize_sums(const double* sums, int C, double count, f
 // activations: used when a forward pass is replayed from cached activations (the decoder passes that the
 // reference recomputes with unchanged weights, train_soft_intro_vae.py:557 vs :597 and :561 vs :598) so that
 // running_mean / running_var / num_batches_tracked still receive exactly one update per reference pass.
-__global__ void __launch_bounds__(64) bn_update_running_kernel(const float* __restrict__ mean,
-                                                               const float* __restrict__ invstd, int C, double count,
-                                                               float eps, float momentum, float* running_mean,
-                                                               float* running_var, long long* num_batches_tracked) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
-  if (c >= C) return;
-  const double is = (double)invstd[c];
-  double var = 1.0 / (is * is) - (double)eps;
-  if (var < 0.0) var = 0.0;
-  const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-  running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * (double)mean[c]);
-  running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
-}
-
-// segmented replay: mean / invstd [nseg][C], one momentum update per pass (seg_rev: last pass first)
+// mean / invstd [nseg][C], one momentum update per pass (seg_rev: last pass first); nseg = 1 is the plain replay.
 __global__ void __launch_bounds__(64) bn_update_running_seg_kernel(const float* __restrict__ mean,
                                                                    const float* __restrict__ invstd, int nseg,
                                                                    int seg_rev, int C, double count, float eps,
@@ -445,14 +422,12 @@ extern "C" int sivae_bn_update_running_seg(const float* mean, const float* invst
   return sivae_launch_status();
 }
 
-extern "C" int sivae_bn_update_running(const float* mean, const float* invstd, int C, double count, float eps,
-                                       float momentum, float* running_mean, float* running_var,
-                                       long long* num_batches_tracked, hipStream_t stream) {
-  if (!mean || !invstd || !running_mean || !running_var) return SIVAE_ERR_NULL;
-  if (C <= 0 || count <= 0.0) return SIVAE_ERR_SHAPE;
-  hipLaunchKernelGGL(bn_update_running_kernel, dim3(cdiv(C, 64)), dim3(64), 0, stream, mean, invstd, C, count, eps,
-                     momentum, running_mean, running_var, num_batches_tracked);
-  return sivae_launch_status();
+// One segment is no segmentation: seg_images == B reaches the kernels as segB = 0 (statistics indexed by the channel
+// alone, no per-element segment division).  false: seg_images does not cut the B images into whole segments.
+static bool normalise_segments(int B, int& segB) {
+  if (segB < 0 || (segB > 0 && B % segB != 0)) return false;
+  if (segB == B) segB = 0;
+  return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -514,10 +489,10 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__
 
 static int bn_apply_impl(const float* x, const float* res, const float* mean, const float* invstd,
                          const float* gamma, const float* beta, float slope, float* y, unsigned char* mask, int B,
-                         int C, int HW, hipStream_t stream, int segB = 0) {
+                         int C, int HW, hipStream_t stream, int segB) {
   if (!x || !mean || !invstd || !gamma || !beta || !y) return SIVAE_ERR_NULL;
   if (B <= 0 || C <= 0 || HW <= 0) return SIVAE_ERR_SHAPE;
-  if (segB < 0 || (segB > 0 && B % segB != 0)) return SIVAE_ERR_SHAPE;
+  if (!normalise_segments(B, segB)) return SIVAE_ERR_SHAPE;
   const size_t numel = (size_t)B * C * HW;
   const bool vec = (HW & 3) == 0;
   if (mask && !vec) return SIVAE_ERR_SHAPE;
@@ -535,12 +510,6 @@ static int bn_apply_impl(const float* x, const float* res, const float* mean, co
   }
 #undef LAUNCH
   return sivae_launch_status();
-}
-
-extern "C" int sivae_bn_apply_act(const float* x, const float* res, const float* mean, const float* invstd,
-                                  const float* gamma, const float* beta, float slope, float* y, int B, int C,
-                                  int HW, hipStream_t stream) {
-  return bn_apply_impl(x, res, mean, invstd, gamma, beta, slope, y, nullptr, B, C, HW, stream);
 }
 
 // Same op with the residual stored at HALF resolution and read through nn.Upsample(2,'nearest') addressing
@@ -587,10 +556,10 @@ __global__ void __launch_bounds__(256) bn_apply_resup_kernel(const float* __rest
 
 static int bn_apply_resup_impl(const float* x, const float* res_half, const float* mean, const float* invstd,
                                const float* gamma, const float* beta, float slope, float* y, unsigned char* mask,
-                               int B, int C, int H, int W, hipStream_t stream, int segB = 0) {
+                               int B, int C, int H, int W, hipStream_t stream, int segB) {
   if (!x || !res_half || !mean || !invstd || !gamma || !beta || !y) return SIVAE_ERR_NULL;
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 3)) return SIVAE_ERR_SHAPE;
-  if (segB < 0 || (segB > 0 && B % segB != 0)) return SIVAE_ERR_SHAPE;
+  if (!normalise_segments(B, segB)) return SIVAE_ERR_SHAPE;
   const size_t numel = (size_t)B * C * H * W;
   int nb = cdiv((long long)(numel >> 2), 256 * 4);
   if (nb > 8192) nb = 8192;
@@ -598,12 +567,6 @@ static int bn_apply_resup_impl(const float* x, const float* res_half, const floa
   hipLaunchKernelGGL(bn_apply_resup_kernel, dim3(nb), dim3(256), 0, stream, x, res_half, mean, invstd, gamma, beta,
                      slope, y, mask, C, H, W, numel, segB);
   return sivae_launch_status();
-}
-
-extern "C" int sivae_bn_apply_act_resup(const float* x, const float* res_half, const float* mean, const float* invstd,
-                                        const float* gamma, const float* beta, float slope, float* y, int B, int C,
-                                        int H, int W, hipStream_t stream) {
-  return bn_apply_resup_impl(x, res_half, mean, invstd, gamma, beta, slope, y, nullptr, B, C, H, W, stream);
 }
 
 // Same op, also writing AvgPool2d(2) of the result (the pool that follows every encoder block and the stem,
@@ -668,10 +631,10 @@ __global__ void __launch_bounds__(256) bn_apply_pool_kernel(const float* __restr
 
 static int bn_apply_pool_impl(const float* x, const float* res, const float* mean, const float* invstd,
                               const float* gamma, const float* beta, float slope, float* y, float* y_pooled,
-                              unsigned char* mask, int B, int C, int H, int W, hipStream_t stream, int segB = 0) {
+                              unsigned char* mask, int B, int C, int H, int W, hipStream_t stream, int segB) {
   if (!x || !mean || !invstd || !gamma || !beta || !y_pooled) return SIVAE_ERR_NULL;  // y may be NULL: pooled only
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 3)) return SIVAE_ERR_SHAPE;
-  if (segB < 0 || (segB > 0 && B % segB != 0)) return SIVAE_ERR_SHAPE;
+  if (!normalise_segments(B, segB)) return SIVAE_ERR_SHAPE;
   if (mask && (W & 7)) return SIVAE_ERR_SHAPE;
   const size_t n_quads = (size_t)B * C * (H >> 1) * (W >> 2);
   int nb = cdiv((long long)n_quads, 256 * 2);
@@ -686,27 +649,15 @@ static int bn_apply_pool_impl(const float* x, const float* res, const float* mea
   return sivae_launch_status();
 }
 
-extern "C" int sivae_bn_apply_act_pool(const float* x, const float* res, const float* mean, const float* invstd,
-                                       const float* gamma, const float* beta, float slope, float* y, float* y_pooled,
-                                       int B, int C, int H, int W, hipStream_t stream) {
-  return bn_apply_pool_impl(x, res, mean, invstd, gamma, beta, slope, y, y_pooled, nullptr, B, C, H, W, stream);
-}
-
-// ---- the three apply flavours with the LeakyReLU sign mask as an extra output (see sign_nibble above):
+// ---- the two apply entry points.  B = nseg * seg_images images: several passes of a network through the same weights
+// run as ONE batch with per-pass BatchNorm statistics (functional.py "segments"; mean / invstd are [nseg][C], gamma /
+// beta [C]); seg_images == B is the unsegmented op.  Three flavours:
 //   y_pooled != NULL : BatchNorm + residual + LeakyReLU + AvgPool2d(2); y (full resolution) may be NULL
 //   res_up != 0      : residual at half resolution, read through Upsample(2,'nearest') addressing
-//   otherwise        : plain apply.           mask: sivae_bn_signmask_bytes(B, C, H*W) bytes.  H even, W % 8 == 0.
-extern "C" size_t sivae_bn_signmask_bytes(int B, int C, int HW) {
-  if (B <= 0 || C <= 0 || HW <= 0) return 0;
-  return ((size_t)B * C * HW + 7) / 8;
-}
-
-static int bn_apply_signmask_impl(const float* x, const float* res, int res_up, const float* mean,
-                                  const float* invstd, const float* gamma, const float* beta, float slope, float* y,
-                                  float* y_pooled, unsigned char* mask, int B, int C, int H, int W, int segB,
-                                  hipStream_t stream) {
-  if (!mask) return SIVAE_ERR_NULL;
-  if (H <= 0 || W <= 0 || (H & 1) || (W & 7)) return SIVAE_ERR_SHAPE;
+//   otherwise        : plain apply (H, W only as H * W)
+static int bn_apply_any(const float* x, const float* res, int res_up, const float* mean, const float* invstd,
+                        const float* gamma, const float* beta, float slope, float* y, float* y_pooled,
+                        unsigned char* mask, int B, int C, int H, int W, int segB, hipStream_t stream) {
   if (y_pooled) {
     if (res_up) return SIVAE_ERR_MODE;
     return bn_apply_pool_impl(x, res, mean, invstd, gamma, beta, slope, y, y_pooled, mask, B, C, H, W, stream, segB);
@@ -715,39 +666,31 @@ static int bn_apply_signmask_impl(const float* x, const float* res, int res_up, 
   return bn_apply_impl(x, res, mean, invstd, gamma, beta, slope, y, mask, B, C, H * W, stream, segB);
 }
 
-extern "C" int sivae_bn_apply_act_signmask(const float* x, const float* res, int res_up, const float* mean,
-                                           const float* invstd, const float* gamma, const float* beta, float slope,
-                                           float* y, float* y_pooled, unsigned char* mask, int B, int C, int H, int W,
-                                           hipStream_t stream) {
-  return bn_apply_signmask_impl(x, res, res_up, mean, invstd, gamma, beta, slope, y, y_pooled, mask, B, C, H, W, 0,
-                                stream);
-}
-
-// ---- segmented forms (B = nseg * seg_images images; mean / invstd are [nseg][C], gamma / beta [C]): several passes of a
-// network through the same weights run as ONE batch with per-pass BatchNorm statistics (functional.py "segments")
-extern "C" int sivae_bn_apply_act_signmask_seg(const float* x, const float* res, int res_up, const float* mean,
-                                               const float* invstd, const float* gamma, const float* beta, float slope,
-                                               float* y, float* y_pooled, unsigned char* mask, int B, int C, int H,
-                                               int W, int seg_images, hipStream_t stream) {
-  if (seg_images <= 0) return SIVAE_ERR_SHAPE;
-  return bn_apply_signmask_impl(x, res, res_up, mean, invstd, gamma, beta, slope, y, y_pooled, mask, B, C, H, W,
-                                seg_images, stream);
-}
-
-// plain apply (+ residual; res_up: residual at half resolution; y_pooled != NULL: also AvgPool2d(2), y may be NULL)
 extern "C" int sivae_bn_apply_act_seg(const float* x, const float* res, int res_up, const float* mean,
                                       const float* invstd, const float* gamma, const float* beta, float slope,
                                       float* y, float* y_pooled, int B, int C, int H, int W, int seg_images,
                                       hipStream_t stream) {
   if (seg_images <= 0) return SIVAE_ERR_SHAPE;
-  if (y_pooled) {
-    if (res_up) return SIVAE_ERR_MODE;
-    return bn_apply_pool_impl(x, res, mean, invstd, gamma, beta, slope, y, y_pooled, nullptr, B, C, H, W, stream,
-                              seg_images);
-  }
-  if (res_up)
-    return bn_apply_resup_impl(x, res, mean, invstd, gamma, beta, slope, y, nullptr, B, C, H, W, stream, seg_images);
-  return bn_apply_impl(x, res, mean, invstd, gamma, beta, slope, y, nullptr, B, C, H * W, stream, seg_images);
+  return bn_apply_any(x, res, res_up, mean, invstd, gamma, beta, slope, y, y_pooled, nullptr, B, C, H, W, seg_images,
+                      stream);
+}
+
+// the same with the LeakyReLU sign mask as an extra output (see sign_nibble above): sivae_bn_signmask_bytes(B, C, H*W)
+// bytes.  H even, W % 8 == 0.
+extern "C" size_t sivae_bn_signmask_bytes(int B, int C, int HW) {
+  if (B <= 0 || C <= 0 || HW <= 0) return 0;
+  return ((size_t)B * C * HW + 7) / 8;
+}
+
+extern "C" int sivae_bn_apply_act_signmask_seg(const float* x, const float* res, int res_up, const float* mean,
+                                               const float* invstd, const float* gamma, const float* beta, float slope,
+                                               float* y, float* y_pooled, unsigned char* mask, int B, int C, int H,
+                                               int W, int seg_images, hipStream_t stream) {
+  if (seg_images <= 0) return SIVAE_ERR_SHAPE;
+  if (!mask) return SIVAE_ERR_NULL;
+  if (H <= 0 || W <= 0 || (H & 1) || (W & 7)) return SIVAE_ERR_SHAPE;
+  return bn_apply_any(x, res, res_up, mean, invstd, gamma, beta, slope, y, y_pooled, mask, B, C, H, W, seg_images,
+                      stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1017,8 +960,8 @@ __global__ void __launch_bounds__(256) bn_bwd_dx_dzsum_kernel(const float* __res
 static int bn_bwd_impl(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
                        const float* gamma, const float* beta, int act_mode, float slope, float* dx, float* dz_out,
                        float* dgamma, float* dbeta, int B, int C, int HW, int pool_w, void* workspace,
-                       size_t workspace_bytes, hipStream_t stream, int dzsum_w = 0,
-                       const unsigned char* mask = nullptr, int segB = 0, unsigned* counters = nullptr) {
+                       size_t workspace_bytes, hipStream_t stream, int dzsum_w, const unsigned char* mask,
+                       int segB, unsigned* counters) {
   // segB > 0: B = nseg * segB images, statistics / coefficients per (segment, channel); the workspace layout is the
   // unsegmented one with nseg*C virtual channels (it is sized for (B, C, HW), which covers (segB, nseg*C, HW))
   if (!dy || !x || !mean || !invstd || !gamma || !dx) return SIVAE_ERR_NULL;
@@ -1027,7 +970,7 @@ static int bn_bwd_impl(const float* dy, const float* y, const float* x, const fl
   if (act_mode == 3 && (!mask || (HW & 3))) return SIVAE_ERR_NULL;  // sign from the 1-bit mask (float4 path only)
   if (act_mode == 2 && !beta) return SIVAE_ERR_NULL;
   if (B <= 0 || C <= 0 || HW <= 0) return SIVAE_ERR_SHAPE;
-  if (segB < 0 || (segB > 0 && B % segB != 0)) return SIVAE_ERR_SHAPE;
+  if (!normalise_segments(B, segB)) return SIVAE_ERR_SHAPE;
   const int nseg = segB > 0 ? B / segB : 1, Bs = segB > 0 ? segB : B, VC = nseg * C;
   const long long n = (long long)Bs * HW;
   SlicePlan p = plan_slices(n, VC);
@@ -1077,59 +1020,16 @@ static int bn_bwd_impl(const float* dy, const float* y, const float* x, const fl
   return sivae_launch_status();
 }
 
-extern "C" int sivae_bn_bwd(const float* dy, const float* y, const float* x, const float* mean,
-                            const float* invstd, const float* gamma, const float* beta, int act_mode,
-                            float slope, float* dx, float* dz_out, float* dgamma, float* dbeta, int B, int C,
-                            int HW, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return bn_bwd_impl(dy, y, x, mean, invstd, gamma, beta, act_mode, slope, dx, dz_out, dgamma, dbeta, B, C, HW, 0,
-                     workspace, workspace_bytes, stream);
-}
-
-// act_mode-1 backward whose residual-branch gradient comes out as its 2x2 block sum dz_half [B][C][H/2][W/2]
-// (the adjoint of the nn.Upsample in front of the block) instead of the full-resolution dz; H even, W % 4 == 0.
-extern "C" int sivae_bn_bwd_dzsum(const float* dy, const float* y, const float* x, const float* mean,
-                                  const float* invstd, const float* gamma, float slope, float* dx, float* dz_half,
-                                  float* dgamma, float* dbeta, int B, int C, int H, int W, void* workspace,
-                                  size_t workspace_bytes, hipStream_t stream) {
-  if (!y || !dz_half) return SIVAE_ERR_NULL;
-  if (H <= 0 || W <= 0 || (H & 1) || (W & 3)) return SIVAE_ERR_SHAPE;
-  return bn_bwd_impl(dy, y, x, mean, invstd, gamma, nullptr, 1, slope, dx, dz_half, dgamma, dbeta, B, C, H * W, 0,
-                     workspace, workspace_bytes, stream, W);
-}
-
-// Same with dy = the gradient of AvgPool2d(2)(y) at half resolution [B][C][H/2][W/2] (H even, W % 4 == 0): the
-// pool's adjoint is applied while reading, so the block backward of "ResidualBlock -> AvgPool2d" (:95-99) and of the
-// stem (:88-93) never materialises the full-resolution gradient.
-extern "C" int sivae_bn_bwd_pooled_dy(const float* dy_half, const float* y, const float* x, const float* mean,
-                                      const float* invstd, const float* gamma, const float* beta, int act_mode,
-                                      float slope, float* dx, float* dz_out, float* dgamma, float* dbeta, int B, int C,
-                                      int H, int W, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (H <= 0 || W <= 0 || (H & 1) || (W & 3)) return SIVAE_ERR_SHAPE;
-  return bn_bwd_impl(dy_half, y, x, mean, invstd, gamma, beta, act_mode, slope, dx, dz_out, dgamma, dbeta, B, C, H * W,
-                     W, workspace, workspace_bytes, stream);
-}
-
-// Backward of "LeakyReLU(BN(x) + res)" with the LeakyReLU sign taken from the 1-bit mask the apply pass wrote
-// (sivae_bn_apply_act_signmask) — 1/32 of a tensor per pass instead of the saved output.  dy_pooled != 0: dy is
-// the gradient of AvgPool2d(2)(output) at half resolution; dz_sum != 0: dz_out is the 2x2 block sum of the
-// residual-branch gradient ([B][C][H/2][W/2]); not both.  H even, W % 8 == 0.
-extern "C" int sivae_bn_bwd_signmask(const float* dy, const unsigned char* mask, const float* x, const float* mean,
-                                     const float* invstd, const float* gamma, float slope, float* dx, float* dz_out,
-                                     float* dgamma, float* dbeta, int B, int C, int H, int W, int dy_pooled, int dz_sum,
-                                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!mask) return SIVAE_ERR_NULL;
-  if (H <= 0 || W <= 0 || (H & 1) || (W & 7)) return SIVAE_ERR_SHAPE;
-  if (dy_pooled && dz_sum) return SIVAE_ERR_MODE;
-  if (dz_sum && !dz_out) return SIVAE_ERR_NULL;
-  return bn_bwd_impl(dy, nullptr, x, mean, invstd, gamma, nullptr, 3, slope, dx, dz_out, dgamma, dbeta, B, C, H * W,
-                     dy_pooled ? W : 0, workspace, workspace_bytes, stream, dz_sum ? W : 0, mask);
-}
-
-// General segmented backward: every variant above with B = nseg * seg_images images and per-(segment, channel)
-// statistics (mean / invstd [nseg][C]); dgamma / dbeta [C] are summed over the segments.
-//   act_mode 0 none, 1 sign from the saved output y, 2 sign recomputed from x (needs beta), 3 sign from `mask`
-//   dy_pooled: dy is the gradient of AvgPool2d(2)(output) ([B][C][H/2][W/2]); dz_sum: dz_out receives the 2x2 block
-//   sums of the residual-branch gradient (act_mode 1 or 3)
+// The three-launch backward, every variant: B = nseg * seg_images images and per-(segment, channel) statistics (mean /
+// invstd [nseg][C]); dgamma / dbeta [C] are summed over the segments; seg_images == B is the unsegmented op.
+//   act_mode 0 none, 1 sign from the saved output y, 2 sign recomputed from x (needs beta), 3 sign from the 1-bit `mask`
+//   the apply pass wrote (1/32 of a tensor per pass instead of the saved output; H even, W % 8 == 0)
+//   dy_pooled: dy is the gradient of AvgPool2d(2)(output) at half resolution [B][C][H/2][W/2]; the pool's adjoint is
+//   applied while reading, so the block backward of "ResidualBlock -> AvgPool2d" (:95-99) and of the stem (:88-93) never
+//   materialises the full-resolution gradient
+//   dz_sum: dz_out receives the 2x2 block sums [B][C][H/2][W/2] of the residual-branch gradient (the adjoint of the
+//   nn.Upsample in front of a decoder block) instead of the full-resolution dz (act_mode 1 or 3)
+//   dy_pooled, dz_sum: H even, W % 4 == 0, not both
 //   counters: NULL, or >= C zero-initialised unsigned ints that this call leaves zero: the per-channel finalize then runs
 //   inside the reduction kernel (last block of a channel) instead of as a launch of its own; a counter buffer must not
 //   be shared by calls running concurrently on different streams

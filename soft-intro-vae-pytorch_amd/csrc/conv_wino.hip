@@ -671,7 +671,7 @@ extern "C" int sivae_conv2d_wino_fwd_seg(const float* x, const float* up, float*
 
 // Data-gradient use feeding a BatchNorm backward: y = dL/dh with h = LeakyReLU(BatchNorm(bn_x)) (bn_x has y's shape);
 // bnbwd_partial [sivae_conv2d_wino_num_px_tiles][Co][2] receives per tile {sum g, sum g * xhat}, g = y * LeakyReLU'(z)
-// — the first reduction of sivae_bn_bwd (see sivae_bn_bwd_from_partials).
+// — the first reduction of sivae_bn_bwd_seg (see sivae_bn_bwd_from_partials).
 extern "C" int sivae_conv2d_wino_dgrad_bnbwd(const float* dy, const float* up, float* y, const float* bn_x,
                                              const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                              const float* bn_beta, float slope, float* bnbwd_partial, int B, int Ci,

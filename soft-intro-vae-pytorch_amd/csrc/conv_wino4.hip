@@ -276,7 +276,7 @@ extern "C" int sivae_conv2d_wino4_num_px_tiles(int B, int H, int W) {
 }
 
 // y[B][Co][H][W] (+)= conv3x3(x, U);  stats_partial (optional): [sivae_conv2d_wino4_num_px_tiles][Co][2] per-tile {sum, sumsq}
-// of y in image order (sivae_bn_stats_from_conv / _seg).  The data gradient is this function on dy with the mode-1 pack.
+// of y in image order (sivae_bn_stats_from_conv_ws / _seg).  The data gradient is this function on dy with the mode-1 pack.
 static int wino4_impl(const float* x, const float* up, float* y, const float* pro_mean, const float* pro_invstd,
                       const float* pro_gamma, const float* pro_beta, float pro_slope, float* stats_partial, int B, int Ci,
                       int Co, int H, int W, int accumulate, int seg_images, hipStream_t stream, int ksl = 1,

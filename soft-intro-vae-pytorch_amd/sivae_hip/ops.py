@@ -569,8 +569,8 @@ def conv2d_up_dgrad_route(B, C, N, H, W, *, has_wp1=False):
 
 def bn_bwd_route(B, C, H, W, *, op="bn_bwd", four_d=True, dy_pooled=False, nseg=1):
     """route of bn_bwd / bn_bwd_signmask / bn_bwd_dzsum (op: "bn_bwd", "signmask", "dzsum") for x [B, C, H, W] (four_d
-    False: x is [B, C] or flat, H * W elements per channel and image).  Three tiers: the one-launch persistent kernel,
-    the segmented / fused-finalize form, the plain form of `op`."""
+    False: x is [B, C] or flat, H * W elements per channel and image): the one-launch persistent kernel, the
+    synchronised pair, or the three-launch form that takes every variant (nseg = 1: seg_images == B, the plain op)."""
     L = _lib.load()
     sync = SYNC_BN is not None
     # (shapes / modes the fused read of a pooled dy does not cover: the pool's adjoint runs first)
@@ -581,20 +581,15 @@ def bn_bwd_route(B, C, H, W, *, op="bn_bwd", four_d=True, dy_pooled=False, nseg=
             and L.sivae_bn_bwd_fused_supported(B, C, H, W, B // nseg) == 1):
         return Route("bn_fused", "sivae_bn_bwd_fused", materialise=expand,
                      ws_bytes=L.sivae_bn_bwd_fused_workspace_bytes(B, C, H, W, B // nseg))
-    if nseg > 1 or (BN_FUSED_FINALIZE and not sync and four_d):
-        if sync:
-            return Route("bn_seg", "sivae_bn_bwd_seg", materialise=expand, error=(
-                RuntimeError, "sivae_hip: segmented batches and synchronised BatchNorm do not combine"))
-        return Route("bn_seg", "sivae_bn_bwd_seg", materialise=expand,
-                     ws_bytes=L.sivae_bn_workspace_bytes(B // nseg, nseg * C, H * W))
-    ws = L.sivae_bn_workspace_bytes(B, C, H * W)
-    if op != "bn_bwd":
-        return Route("bn_" + op, "sivae_bn_bwd_" + op, ws_bytes=ws)
-    if sync:
+    if sync and nseg > 1:
+        return Route("bn_seg", "sivae_bn_bwd_seg", materialise=expand, error=(
+            RuntimeError, "sivae_hip: segmented batches and synchronised BatchNorm do not combine"))
+    ws = L.sivae_bn_workspace_bytes(B // nseg, nseg * C, H * W)
+    # (the sync pair has no mask / block-sum argument: bn_signmask_supported / bn_bwd_dzsum_supported keep those ops
+    # away under SYNC_BN, and a direct call of them gets the local statistics of the three-launch form)
+    if sync and op == "bn_bwd":
         return Route("bn_sync", "sivae_bn_bwd_reduce", materialise=expand, ws_bytes=ws)
-    if dy_pooled and not expand:
-        return Route("bn_pooled_dy", "sivae_bn_bwd_pooled_dy", ws_bytes=ws)
-    return Route("bn_plain", "sivae_bn_bwd", materialise=expand, ws_bytes=ws)
+    return Route("bn_seg", "sivae_bn_bwd_seg", materialise=expand, ws_bytes=ws)
 
 
 def _prologue(pro):
@@ -888,13 +883,9 @@ def bn_stats_from_conv(partials, B, C, HW, running_mean=None, running_var=None, 
 def bn_update_running(mean, invstd, count, running_mean, running_var, num_batches_tracked, eps=1e-5, momentum=0.1,
                       nseg=1, seg_rev=False):
     _require(mean, invstd, running_mean, running_var, num_batches_tracked)
-    if nseg > 1:
-        _lib.call("sivae_bn_update_running_seg", _p(mean), _p(invstd), nseg, int(bool(seg_rev)), mean.numel() // nseg,
-                  float(count), float(eps), float(momentum), _p(running_mean), _p(running_var),
-                  _p(num_batches_tracked), _s())
-        return
-    _lib.call("sivae_bn_update_running", _p(mean), _p(invstd), mean.numel(), float(count), float(eps),
-              float(momentum), _p(running_mean), _p(running_var), _p(num_batches_tracked), _s())
+    _lib.call("sivae_bn_update_running_seg", _p(mean), _p(invstd), nseg, int(bool(seg_rev)), mean.numel() // nseg,
+              float(count), float(eps), float(momentum), _p(running_mean), _p(running_var), _p(num_batches_tracked),
+              _s())
 
 
 def bn_apply_act(x, res, mean, invstd, gamma, beta, slope=LRELU_SLOPE, out=None, res_up=False, nseg=1):
@@ -903,19 +894,11 @@ def bn_apply_act(x, res, mean, invstd, gamma, beta, slope=LRELU_SLOPE, out=None,
     B, C = x.shape[0], x.shape[1]
     HW = x.numel() // (B * C)
     y = out if out is not None else torch.empty_like(x)
-    if nseg > 1:
-        H, W = (x.shape[2], x.shape[3]) if x.dim() == 4 else (1, HW)
-        _lib.call("sivae_bn_apply_act_seg", _p(x), _p(res), int(bool(res_up)), _p(mean), _p(invstd), _p(gamma),
-                  _p(beta), float(slope), _p(y), None, B, C, H, W, B // nseg, _s())
-        return y
+    H, W = (x.shape[2], x.shape[3]) if x.dim() == 4 else (1, HW)
     if res_up:
-        H, W = x.shape[2], x.shape[3]
         assert res.shape == (B, C, H // 2, W // 2)
-        _lib.call("sivae_bn_apply_act_resup", _p(x), _p(res), _p(mean), _p(invstd), _p(gamma), _p(beta), float(slope),
-                  _p(y), B, C, H, W, _s())
-        return y
-    _lib.call("sivae_bn_apply_act", _p(x), _p(res), _p(mean), _p(invstd), _p(gamma), _p(beta), float(slope), _p(y),
-              B, C, HW, _s())
+    _lib.call("sivae_bn_apply_act_seg", _p(x), _p(res), int(bool(res_up)), _p(mean), _p(invstd), _p(gamma), _p(beta),
+              float(slope), _p(y), None, B, C, H, W, B // nseg, _s())
     return y
 
 
@@ -928,12 +911,8 @@ def bn_apply_act_pool(x, res, mean, invstd, gamma, beta, slope=LRELU_SLOPE, want
     _require(x, res, mean, invstd, gamma, beta)
     y = torch.empty_like(x) if want_full else None
     yp = torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
-    if nseg > 1:
-        _lib.call("sivae_bn_apply_act_seg", _p(x), _p(res), 0, _p(mean), _p(invstd), _p(gamma), _p(beta), float(slope),
-                  _p(y), _p(yp), B, C, H, W, B // nseg, _s())
-        return y, yp
-    _lib.call("sivae_bn_apply_act_pool", _p(x), _p(res), _p(mean), _p(invstd), _p(gamma), _p(beta), float(slope),
-              _p(y), _p(yp), B, C, H, W, _s())
+    _lib.call("sivae_bn_apply_act_seg", _p(x), _p(res), 0, _p(mean), _p(invstd), _p(gamma), _p(beta), float(slope),
+              _p(y), _p(yp), B, C, H, W, B // nseg, _s())
     return y, yp
 
 
@@ -952,12 +931,8 @@ def bn_apply_act_signmask(x, res, mean, invstd, gamma, beta, slope=LRELU_SLOPE, 
     y = torch.empty_like(x) if want_full else None
     yp = torch.empty((B, C, H // 2, W // 2), dtype=torch.float32, device=x.device) if pool else None
     mask = torch.empty(_lib.load().sivae_bn_signmask_bytes(B, C, H * W), dtype=torch.uint8, device=x.device)
-    if nseg > 1:
-        _lib.call("sivae_bn_apply_act_signmask_seg", _p(x), _p(res), int(bool(res_up)), _p(mean), _p(invstd),
-                  _p(gamma), _p(beta), float(slope), _p(y), _p(yp), _p(mask), B, C, H, W, B // nseg, _s())
-        return y, yp, mask
-    _lib.call("sivae_bn_apply_act_signmask", _p(x), _p(res), int(bool(res_up)), _p(mean), _p(invstd), _p(gamma),
-              _p(beta), float(slope), _p(y), _p(yp), _p(mask), B, C, H, W, _s())
+    _lib.call("sivae_bn_apply_act_signmask_seg", _p(x), _p(res), int(bool(res_up)), _p(mean), _p(invstd), _p(gamma),
+              _p(beta), float(slope), _p(y), _p(yp), _p(mask), B, C, H, W, B // nseg, _s())
     return y, yp, mask
 
 
@@ -981,25 +956,7 @@ def _bn_bwd_run(op, dy, y, mask, x, mean, invstd, gamma, beta, act_mode, slope, 
         dz = torch.empty_like(x)
     dgamma, dbeta = _pg(pg_out, C, x.device, want_param_grads)
     ws = workspace(r.ws_bytes, x.device)
-    # (every variant, segmented or not, that the two general entry points take)
-    general = (_p(dy), _p(y), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode), float(slope),
-               _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)), int(bool(dz_sum)), B // nseg)
-    seg = r.family == "bn_seg"
-    if r.family == "bn_fused":
-        try:
-            _lib.call(r.entry, *general, _p(bn_fused_state(x.device)), _p(ws), ws.numel(), _s(x))
-        except _lib.SivaeError as e:
-            if e.code != -2:
-                raise
-            # a shape the plan of this variant does not take after all (the query and the launch plan with the same
-            # register budget since round 5, so this is a safety net): the three-launch form takes every shape
-            seg, ws = True, workspace(_lib.load().sivae_bn_workspace_bytes(B // nseg, nseg * C, H * W), x.device)
-        else:
-            return dx, dz, dgamma, dbeta
-    if seg:  # the per-channel finalize fused into the reduction kernel
-        cnt = counters(x.device) if (BN_FUSED_FINALIZE and C <= 8192) else None
-        _lib.call("sivae_bn_bwd_seg", *general, _p(cnt), _p(ws), ws.numel(), _s())
-    elif r.family == "bn_sync":
+    if r.family == "bn_sync":
         local = torch.empty((C, 2), dtype=torch.float64, device=x.device)
         _lib.call(r.entry, _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode), float(slope),
                   _p(local), B, C, H * W, _p(ws), ws.numel(), _s())
@@ -1008,16 +965,24 @@ def _bn_bwd_run(op, dy, y, mask, x, mean, invstd, gamma, beta, act_mode, slope, 
         _lib.call("sivae_bn_bwd_apply", _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta),
                   int(act_mode), float(slope), _p(local), _p(glob), float(B) * H * W * world, _p(dx), _p(dz),
                   _p(dgamma), _p(dbeta), B, C, H * W, _p(ws), ws.numel(), _s())
-    elif r.family == "bn_signmask":
-        _lib.call(r.entry, _p(dy), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), float(slope), _p(dx), _p(dz),
-                  _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)), int(bool(dz_sum)), _p(ws), ws.numel(), _s())
-    elif r.family == "bn_dzsum":
-        _lib.call(r.entry, _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), float(slope), _p(dx), _p(dz),
-                  _p(dgamma), _p(dbeta), B, C, H, W, _p(ws), ws.numel(), _s())
-    else:  # sivae_bn_bwd (sizes B, C, H * W) / sivae_bn_bwd_pooled_dy (B, C, H, W)
-        _lib.call(r.entry, _p(dy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode), float(slope),
-                  _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, *((H, W) if dy_pooled else (H * W,)), _p(ws),
-                  ws.numel(), _s())
+        return dx, dz, dgamma, dbeta
+    # (every variant, segmented or not, that the two general entry points take)
+    general = (_p(dy), _p(y), _p(mask), _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), int(act_mode), float(slope),
+               _p(dx), _p(dz), _p(dgamma), _p(dbeta), B, C, H, W, int(bool(dy_pooled)), int(bool(dz_sum)), B // nseg)
+    if r.family == "bn_fused":
+        try:
+            _lib.call(r.entry, *general, _p(bn_fused_state(x.device)), _p(ws), ws.numel(), _s(x))
+            return dx, dz, dgamma, dbeta
+        except _lib.SivaeError as e:
+            if e.code != -2:
+                raise
+            # a shape the plan of this variant does not take after all (the query and the launch plan with the same
+            # register budget since round 5, so this is a safety net): the three-launch form takes every shape
+            ws = workspace(_lib.load().sivae_bn_workspace_bytes(B // nseg, nseg * C, H * W), x.device)
+    # SIVAE_BN_FUSED_FINALIZE: the per-channel finalize runs inside the reduction kernel (a dead end kept behind its
+    # switch: local statistics only, and a flat or [B, C] input only when it is segmented)
+    fin = BN_FUSED_FINALIZE and C <= 8192 and SYNC_BN is None and (nseg > 1 or x.dim() == 4)
+    _lib.call("sivae_bn_bwd_seg", *general, _p(counters(x.device) if fin else None), _p(ws), ws.numel(), _s())
     return dx, dz, dgamma, dbeta
 
 

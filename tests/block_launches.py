@@ -20,6 +20,8 @@ caches and the pack caches compare data_ptr()).
     python tests/block_launches.py            # writes tests/golden/block_launches.json.gz
     python tests/block_launches.py --trace    # also lists the lines of the block Functions that never ran
 
+The committed fixture was recorded on the commit that folded the per-variant fp32 BatchNorm entry points into the general
+ones (every fp32 BatchNorm apply / replay call is a _seg entry with seg_images = B // nseg).
 tests/test_block_launches_host.py replays it in-process and compares with the committed fixture.
 """
 import contextlib

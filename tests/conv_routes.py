@@ -15,6 +15,8 @@ The module patches only names that are part of the package's surface, so the sam
 
     python tests/conv_routes.py            # writes tests/golden/conv_routes_fp32.json.gz
 
+The committed fixture was recorded on the commit that folded the per-variant fp32 BatchNorm entry points into the general
+ones (bn_bwd_route families bn_fused / bn_sync / bn_seg).
 tests/test_conv_routes_host.py replays it in-process and compares with the committed fixture.
 """
 import contextlib

@@ -356,6 +356,37 @@ def check_bn_from_conv():
     return res
 
 
+def check_bn_update_running():
+    """ops.bn_update_running (the running-buffer replay from saved statistics; every replayed pass goes through it) against
+    the CPU in fp64 from the same fp32 inputs: var = 1 / invstd^2 - eps, unbiased by count / (count - 1), one momentum
+    update per segment in pass order (seg_rev: last pass first) with the buffers rounded to fp32 after each segment —
+    what nn.BatchNorm2d leaves after that many calls.  C = 70 is ragged against the kernel's 64-thread block; eps and
+    momentum are the fp32 values the C ABI carries.  Tolerances: check_bn's for the same buffers."""
+    from sivae_hip import ops
+    C, count = 70, 4 * 6 * 6
+    eps, mom = float(torch.tensor(1e-5, dtype=torch.float32)), float(torch.tensor(0.1, dtype=torch.float32))
+    res = []
+    for nseg, rev in ((1, False), (2, False), (2, True)):
+        g = torch.Generator().manual_seed(70 + nseg)
+        mean = torch.randn(nseg * C, generator=g)
+        invstd = 0.5 + 2.5 * torch.rand(nseg * C, generator=g)  # in [0.5, 3]: the recovered variance is well above zero
+        rm = torch.full((C,), 0.3, device=DEV)
+        rv = torch.full((C,), 1.7, device=DEV)
+        nbt = torch.full((), 5, dtype=torch.int64, device=DEV)
+        rm_ref, rv_ref = rm.double().cpu(), rv.double().cpu()
+        for gi in (reversed(range(nseg)) if rev else range(nseg)):
+            m, i = mean[gi * C:(gi + 1) * C].double(), invstd[gi * C:(gi + 1) * C].double()
+            var = (1.0 / (i * i) - eps) * count / (count - 1)
+            rm_ref = ((1.0 - mom) * rm_ref + mom * m).float().double()
+            rv_ref = ((1.0 - mom) * rv_ref + mom * var).float().double()
+        ops.bn_update_running(mean.to(DEV), invstd.to(DEV), count, rm, rv, nbt, nseg=nseg, seg_rev=rev)
+        tag = "(nseg=%d%s)" % (nseg, ",rev" if rev else "")
+        res.append(("bn_update_running_mean" + tag, _err(rm, rm_ref), 1e-6))
+        res.append(("bn_update_running_var" + tag, _err(rv, rv_ref), 1e-5))
+        res.append(("bn_update_running_nbt" + tag, float(abs(int(nbt.item()) - (5 + nseg))), 0.0))
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ eltwise
 def check_eltwise():
     from sivae_hip import ops
@@ -1698,6 +1729,7 @@ def all_checks():
         checks.append(("bn%s" % (s,), lambda s=s: check_bn(s, False)))
         checks.append(("bn+res%s" % (s,), lambda s=s: check_bn(s, True)))
     checks.append(("bn_from_conv", check_bn_from_conv))
+    checks.append(("bn_update_running", check_bn_update_running))
     checks.append(("eltwise", check_eltwise))
     checks.append(("input_u8", check_input_u8))
     checks.append(("bn_bwd_pooled", check_bn_bwd_pooled))

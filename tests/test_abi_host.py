@@ -38,8 +38,11 @@ def test_argument_errors_use_documented_codes():
     assert L.sivae_conv2d_fwd(one, one, one, null, null, null, null, null, 0.2, null, 1, 1, 1, 5, 5, 3, 1, 0, null) == -2
     assert L.sivae_conv2d_fwd(one, one, one, null, one, null, null, null, 0.2, null, 1, 1, 1, 4, 4, 3, 0, 0, null) == -1
     assert L.sivae_conv2d_wgrad(one, one, one, null, null, null, null, 0.2, 1, 8, 8, 4, 4, 3, 0, null, 0, null) == -4
-    assert L.sivae_bn_bwd(one, null, one, one, one, one, null, 1, 0.2, one, null, null, null, 1, 1, 4, one, 1 << 20, null) == -1
-    assert L.sivae_bn_bwd(one, one, one, one, one, one, null, 7, 0.2, one, null, null, null, 1, 1, 4, one, 1 << 20, null) == -6
+    # (act_mode 1 without the saved output / an act_mode that does not exist)
+    assert L.sivae_bn_bwd_seg(one, null, null, one, one, one, one, null, 1, 0.2, one, null, null, null, 1, 1, 1, 4, 0, 0, 1,
+                              null, one, 1 << 20, null) == -1
+    assert L.sivae_bn_bwd_seg(one, one, null, one, one, one, one, null, 7, 0.2, one, null, null, null, 1, 1, 1, 4, 0, 0, 1,
+                              null, one, 1 << 20, null) == -6
     assert L.sivae_recon_rowsum_fwd(one, one, 9, one, 1, 4, one, 1 << 20, null) == -6
     assert L.sivae_pack_conv_weight(one, one, 4, 4, 7, 0, null) == -3
     assert L.sivae_pack_conv_weight(one, one, 4, 4, 3, 5, null) == -6
@@ -54,12 +57,21 @@ def test_round1_late_entry_points_validate_arguments():
     assert L.sivae_bn_signmask_bytes(2, 3, 16) == 12 and L.sivae_bn_signmask_bytes(1, 1, 4) == 1
     assert L.sivae_bn_signmask_bytes(0, 3, 16) == 0
     # mask missing / W % 8 != 0 / pooled output together with a half-resolution residual
-    assert L.sivae_bn_apply_act_signmask(one, one, 0, one, one, one, one, 0.2, one, null, null, 1, 1, 4, 8, null) == -1
-    assert L.sivae_bn_apply_act_signmask(one, one, 0, one, one, one, one, 0.2, one, null, one, 1, 1, 4, 12, null) == -2
-    assert L.sivae_bn_apply_act_signmask(one, one, 1, one, one, one, one, 0.2, one, one, one, 1, 1, 4, 8, null) == -6
-    assert L.sivae_bn_bwd_signmask(one, null, one, one, one, one, 0.2, one, null, null, null, 1, 1, 4, 8, 0, 0, one, 1 << 20, null) == -1
-    assert L.sivae_bn_bwd_signmask(one, one, one, one, one, one, 0.2, one, one, null, null, 1, 1, 4, 8, 1, 1, one, 1 << 20, null) == -6
-    assert L.sivae_bn_bwd_signmask(one, one, one, one, one, one, 0.2, one, null, null, null, 1, 1, 3, 8, 0, 0, one, 1 << 20, null) == -2
+    assert L.sivae_bn_apply_act_signmask_seg(one, one, 0, one, one, one, one, 0.2, one, null, null, 1, 1, 4, 8, 1, null) == -1
+    assert L.sivae_bn_apply_act_signmask_seg(one, one, 0, one, one, one, one, 0.2, one, null, one, 1, 1, 4, 12, 1, null) == -2
+    assert L.sivae_bn_apply_act_signmask_seg(one, one, 1, one, one, one, one, 0.2, one, one, one, 1, 1, 4, 8, 1, null) == -6
+    # backward with the sign from the mask (act_mode 3): mask missing / pooled dy together with block-summed dz / odd H
+    assert L.sivae_bn_bwd_seg(one, null, null, one, one, one, one, null, 3, 0.2, one, null, null, null, 1, 1, 4, 8, 0, 0, 1,
+                              null, one, 1 << 20, null) == -1
+    assert L.sivae_bn_bwd_seg(one, null, one, one, one, one, one, null, 3, 0.2, one, one, null, null, 1, 1, 4, 8, 1, 1, 1,
+                              null, one, 1 << 20, null) == -6
+    assert L.sivae_bn_bwd_seg(one, null, one, one, one, one, one, null, 3, 0.2, one, null, null, null, 1, 1, 3, 8, 0, 0, 1,
+                              null, one, 1 << 20, null) == -2
+    # seg_images = 0 cuts the batch into no segments: refused by each of the three general entries
+    assert L.sivae_bn_apply_act_seg(one, one, 0, one, one, one, one, 0.2, one, null, 1, 1, 4, 8, 0, null) == -2
+    assert L.sivae_bn_apply_act_signmask_seg(one, one, 0, one, one, one, one, 0.2, one, null, one, 1, 1, 4, 8, 0, null) == -2
+    assert L.sivae_bn_bwd_seg(one, one, null, one, one, one, one, null, 1, 0.2, one, null, null, null, 1, 1, 4, 8, 0, 0, 0,
+                              null, one, 1 << 20, null) == -2
     assert L.sivae_f32_to_u8(null, one, 16, 255.0, null) == -1
     assert L.sivae_f32_to_u8(one, one, 0, 255.0, null) == -2
     assert L.sivae_f32_to_u8(ctypes.c_void_p(20), one, 16, 255.0, null) == -2  # 16-byte alignment

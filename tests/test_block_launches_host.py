@@ -1,9 +1,11 @@
 """Host-only characterisation of the block glue (functional.py / functional16.py): no GPU needed.
 
 tests/block_launches.py drives the real autograd Functions on meta tensors under the recorder of tests/conv_routes.py.
-tests/golden/block_launches.json.gz is what it recorded on the commit BEFORE the blocks were split into a plan and its
-execution (`python tests/block_launches.py` on that commit); a pull request that adds a block form regenerates it from
-the commit that introduces the form.
+tests/golden/block_launches.json.gz is what it recorded (`python tests/block_launches.py`) on the commit that folded the
+per-variant fp32 BatchNorm entry points into the general ones; that recording is the one made BEFORE the blocks were split
+into a plan and its execution with its BatchNorm call records renamed to the general entries and nothing else (DESIGN.md,
+"One BatchNorm entry point per pass").  A pull request that adds a block form regenerates it from the commit that
+introduces the form.
 
 (a) the replay on this tree equals the fixture, record for record: launches, timer events, outputs, saved tensors, slab
     claims, gradient notifications and the backward's return pattern of every Function call;

@@ -1,9 +1,11 @@
 """Host-only checks of the fp32 mode's dispatch (library predicates only: no GPU needed).
 
 tests/conv_routes.py drives the public launch functions of sivae_hip.ops on meta tensors with the C-ABI call replaced by
-a recorder.  tests/golden/conv_routes_fp32.json.gz is what it recorded on the commit BEFORE the dispatch was split into
-route functions and launch bodies (`python tests/conv_routes.py` on that commit); a kernel pull request that changes a
-route regenerates it from the commit that introduces the route.
+a recorder.  tests/golden/conv_routes_fp32.json.gz is what it recorded (`python tests/conv_routes.py`) on the commit that
+folded the per-variant fp32 BatchNorm entry points into the general ones; that recording is the one made BEFORE the
+dispatch was split into route functions and launch bodies with its BatchNorm call records renamed to the general entries
+and nothing else ("One BatchNorm entry point per pass", has the translation table and the comparison).  A
+kernel pull request that changes a route regenerates it from the commit that introduces the route.
 
 (a) the replay on this tree equals the fixture, record for record;
 (b) for every case, the route function names what the launch then does: entry point, timer key, executed FLOPs,
