@@ -36,6 +36,10 @@ struct WinoUpDgArgs {
   int xcd_group;
 };
 
+__device__ __forceinline__ void buf_store_f32(__amdgpu_buffer_rsrc_t r, float v, unsigned voff, unsigned soff) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), r, (int)voff, (int)soff, 0);
+}
+
 #define WUD_CK 16
 #define WUD_TN 128
 
@@ -43,7 +47,9 @@ struct WinoUpDgArgs {
 // KS2 = true (N <= 64): 2 groups of 32 output channels x 2 K-halves — waves 2,3 take k-steps 4..7 of every chunk —
 // so that all four waves work when the layer has only 64 input channels; the two partial outputs (the output
 // transform is linear, so already transformed: 64 floats per lane) are summed through LDS at the end.
-template <int TTH_L2, int TTW_L2, bool KS2>
+// AL8 = false: dx is only 4-byte aligned (a view at an odd element offset of a larger buffer): the output pairs go out as
+// two dword accesses each, same values.
+template <int TTH_L2, int TTW_L2, bool KS2, bool AL8>
 __global__ void __launch_bounds__(256, 2) conv_wino_up_dgrad_kernel(WinoUpDgArgs a) {
   constexpr int TTH = 1 << TTH_L2, TTW = 1 << TTW_L2;
   static_assert(TTH * TTW == 32, "a block is 32 tiles");
@@ -285,15 +291,29 @@ __global__ void __launch_bounds__(256, 2) conv_wino_up_dgrad_kernel(WinoUpDgArgs
           const unsigned cb = base + (unsigned)chn * (unsigned)HWs * 4u;
           const unsigned o0 = (cok && li < Hs) ? cb : SIVAE_OOB;
           const unsigned o1 = (cok && li + 1 < Hs) ? cb + (unsigned)Ws * 4u : SIVAE_OOB;
-          if (a.accumulate) {
-            const float2 p0 = buf_load_f32x2(yrsrc, o0, 0u), p1 = buf_load_f32x2(yrsrc, o1, 0u);
-            y00 += p0.x;
-            y01 += p0.y;
-            y10 += p1.x;
-            y11 += p1.y;
+          if (AL8) {
+            if (a.accumulate) {
+              const float2 p0 = buf_load_f32x2(yrsrc, o0, 0u), p1 = buf_load_f32x2(yrsrc, o1, 0u);
+              y00 += p0.x;
+              y01 += p0.y;
+              y10 += p1.x;
+              y11 += p1.y;
+            }
+            buf_store_f32x2(yrsrc, y00, y01, o0, 0u);
+            buf_store_f32x2(yrsrc, y10, y11, o1, 0u);
+          } else {
+            const unsigned o0b = o0 == SIVAE_OOB ? SIVAE_OOB : o0 + 4u, o1b = o1 == SIVAE_OOB ? SIVAE_OOB : o1 + 4u;
+            if (a.accumulate) {
+              y00 += buf_load_f32(yrsrc, o0, 0u);
+              y01 += buf_load_f32(yrsrc, o0b, 0u);
+              y10 += buf_load_f32(yrsrc, o1, 0u);
+              y11 += buf_load_f32(yrsrc, o1b, 0u);
+            }
+            buf_store_f32(yrsrc, y00, o0, 0u);
+            buf_store_f32(yrsrc, y01, o0b, 0u);
+            buf_store_f32(yrsrc, y10, o1, 0u);
+            buf_store_f32(yrsrc, y11, o1b, 0u);
           }
-          buf_store_f32x2(yrsrc, y00, y01, o0, 0u);
-          buf_store_f32x2(yrsrc, y10, y11, o1, 0u);
         }
       }
       if (KS2) __syncthreads();  // the reduction area aliases the halo buffers of the next item
@@ -470,8 +490,12 @@ static int wud_launch(WinoUpDgArgs& a, hipStream_t stream) {
   a.n_items = (int)nitems;
   const int grid = nitems < wud_grid_blocks() ? (int)nitems : wud_grid_blocks();
   a.xcd_group = (sivae_xcd_remap() && !(grid & 7) && nitems > grid) ? 1 : 0;
-  hipLaunchKernelGGL((conv_wino_up_dgrad_kernel<TTH_L2, TTW_L2, KS2>), dim3((unsigned)grid), dim3(256), lds, stream,
-                     a);
+  if (((uintptr_t)a.dx & 7u) == 0)
+    hipLaunchKernelGGL((conv_wino_up_dgrad_kernel<TTH_L2, TTW_L2, KS2, true>), dim3((unsigned)grid), dim3(256), lds, stream,
+                       a);
+  else
+    hipLaunchKernelGGL((conv_wino_up_dgrad_kernel<TTH_L2, TTW_L2, KS2, false>), dim3((unsigned)grid), dim3(256), lds,
+                       stream, a);
   return sivae_launch_status();
 }
 
@@ -481,7 +505,7 @@ static int wud_run(const float* dy, const float* ud, float* dx, int B, int C, in
   if (!dyp || !ud || !dx) return SIVAE_ERR_NULL;
   if (B <= 0 || C <= 0 || N <= 0 || Hs <= 0 || Ws <= 0) return SIVAE_ERR_SHAPE;
   if (!sivae_conv2d_wino_up_dgrad_supported(Hs, Ws)) return SIVAE_ERR_SHAPE;
-  if (((uintptr_t)dx & 7u) != 0) return SIVAE_ERR_SHAPE;
+  if (((uintptr_t)dx & 3u) != 0) return SIVAE_ERR_SHAPE;  // (8-byte aligned: float2 stores; else the dword form)
   const long long hw = (long long)Hs * Ws;
   if (4ll * C * hw * 4 >= 0x7fffffffLL || (long long)N * hw * 4 >= 0x7fffffffLL) return SIVAE_ERR_RANGE;
   WinoUpDgArgs a;

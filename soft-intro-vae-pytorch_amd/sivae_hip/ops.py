@@ -550,11 +550,13 @@ def conv2d_wgrad_route(B, Ci, Co, H, W, ks, *, pro=False, upsample=False, nseg=1
 
 
 @_memo
-def conv2d_up_dgrad_route(B, C, N, H, W, *, has_wp1=False):
+def conv2d_up_dgrad_route(B, C, N, H, W, *, has_wp1=False, dx_al8=True):
     """route of conv2d_up_dgrad for dy [B, C, H, W] -> dx [B, N, H/2, W/2]; the operand of the wino4_pool family is built
-    from the mode-1 PackedW (wp1), the others from the mode-0 one"""
+    from the mode-1 PackedW (wp1), the others from the mode-0 one.  dx_al8: the destination is 8-byte aligned (every
+    tensor of its own is; a view at an odd element offset is not) — the wino4_pool kernel stores pixel pairs and takes
+    only such destinations, the phase-form kernels take any float32 destination"""
     L = _lib.load()
-    if (WINO4_DGRAD_POOL and WINO4 and has_wp1 and max(C, N) <= WINO4_MAXC
+    if (WINO4_DGRAD_POOL and WINO4 and has_wp1 and dx_al8 and max(C, N) <= WINO4_MAXC
             and L.sivae_conv2d_wino4_dgrad_pool_pays(B, C, N, H, W) == 1):
         return Route("wino4_pool", "sivae_conv2d_wino4_dgrad_pool", "wino4", "a", key="conv_wino4_pool_kernel<false>",
                      ratio=_F44)
@@ -674,7 +676,7 @@ def conv2d_up_dgrad(dy, wp, N, out=None, accumulate=False, wp1=None):
     launches with N <= 64 take the F(4x4,3x3) kernel with the 2x2 block sum folded into its output transform)."""
     _require(dy, out)
     B, C, H, W = dy.shape
-    r = conv2d_up_dgrad_route(B, C, N, H, W, has_wp1=wp1 is not None)
+    r = conv2d_up_dgrad_route(B, C, N, H, W, has_wp1=wp1 is not None, dx_al8=out is None or not (out.data_ptr() & 7))
     dx = _out(out, (B, N, H // 2, W // 2), dy.device)
     t0 = timer_begin()
     _conv_call(r, dy, getattr(wp1 if r.family == "wino4_pool" else wp, r.operand)(), dx, (B, C, N, H, W),

@@ -896,7 +896,32 @@ def check_randn():
            ("randn_std", abs(float(a.std()) - 1.0), 5e-3),
            ("randn_kurt", abs(float((a ** 4).mean()) - 3.0), 5e-2),
            ("randn_stream_indep", abs(float((a * c).mean())), 5e-3)]
+    # stream-position semantics, on which "graph replay == eager" rests: normal j of a draw comes from Philox counter
+    # offset + j // 4 whatever the draw's length (ragged lengths: the last counter's surplus normals are not stored)
+    dev = torch.device(DEV)
+    seed, off = 0x1234567890ABCDEF, (1 << 40) + 12345
+    long_draw = ops.randn((1027,), seed, off, dev)
+    res.append(("randn_finite", float(not torch.isfinite(long_draw).all()), 0.0))
+    for n in (1, 2, 3, 5, 1027):
+        d = ops.randn((n,), seed, off, dev)
+        res.append(("randn_prefix(%d)" % n, _differs(d, long_draw[:n]), 0.0))
+        for k in sorted({0, (n - 1) // 4, (n - 1) // 8}):
+            res.append(("randn_tail(%d,%d)" % (n, k), _differs(d[4 * k:], ops.randn((n - 4 * k,), seed, off + k, dev)), 0.0))
+        pos = torch.tensor([off], dtype=torch.int64, device=dev)
+        res.append(("randn_dev(%d)" % n, _differs(ops.randn_dev((n,), seed, pos, dev), d), 0.0))
+        res.append(("randn_dev_advance(%d)" % n, float(int(pos[0]) != off + (n + 3) // 4), 0.0))
+    from sivae_hip import rng
+    host, devs = rng.PhiloxStream(5, 1), rng.PhiloxStream(5, 1)
+    devs.use_device_state(dev)
+    for shape in ((3, 5), (2, 7)):
+        res.append(("randn_stream_dev_vs_host%s" % (shape,), _differs(devs.randn(shape, dev), host.randn(shape, dev)), 0.0))
+    res.append(("randn_stream_position", float(int(devs.offset_dev[0]) != host.offset or host.offset != 4 + 4), 0.0))
     return res
+
+
+def _differs(a, b):
+    """0.0 when a and b are equal bit for bit as numbers (same shape, no NaN on either side), else 1.0"""
+    return float(not torch.equal(a, b))
 
 
 def check_adam():
@@ -913,8 +938,59 @@ def check_adam():
         opt.step()
         ops.adam_step(pd, g.to(DEV), m, v, step, 2e-4)
     # (the update is ~1e-3 of |p|, so compare p itself: fp32 rounding of p dominates the update error)
-    return [("adam_3steps", _err(pd, pr.detach()), 1e-6),
-            ("adam_3steps_update", _err(pd - p0.to(DEV), pr.detach() - p0), 2e-3)]
+    res = [("adam_3steps", _err(pd, pr.detach()), 1e-6),
+           ("adam_3steps_update", _err(pd - p0.to(DEV), pr.detach() - p0), 2e-3)]
+    # other betas / eps, a gradient scale, one element, one block less and more than 256, a ragged grid: the formula of
+    # optim.hip in fp64 on the same fp32 inputs, at the bounds of the two rows above
+    b1, b2, eps, gs, lrs = 0.5, 0.9, 1e-6, 0.125, (2e-4, 2e-4, 5e-5)
+    for n in (1, 255, 257, 10007):
+        p0 = _rand(n, seed=11).float()
+        gr = [(_rand(n, seed=12 + i) * 8.0).float() for i in range(3)]
+        p64, m64, v64 = p0.double(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+        pd, m, v = p0.to(DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+        # the same three steps with the state on the device (t and the bias corrections advance there; the learning
+        # rate is state[1], changed between steps the way FlatAdam's scheduler hook writes it)
+        pv, mv, vv = p0.to(DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+        state = torch.tensor([0.0, lrs[0], 0.0, 0.0], dtype=torch.float64, device=DEV)
+        same = True
+        for t, (g, lr) in enumerate(zip(gr, lrs), start=1):
+            gi = g.double() * gs
+            m64 = m64 + (1.0 - b1) * (gi - m64)
+            v64 = v64 * b2 + (1.0 - b2) * gi * gi
+            p64 = p64 - (lr / (1.0 - b1 ** t)) * (m64 / (v64.sqrt() / math.sqrt(1.0 - b2 ** t) + eps))
+            ops.adam_step(pd, g.to(DEV), m, v, t, lr, b1, b2, eps, gs)
+            state[1] = lr
+            ops.adam_step_dev(pv, g.to(DEV), mv, vv, state, b1, b2, eps, gs)
+            same = same and torch.equal(pv, pd) and torch.equal(mv, m) and torch.equal(vv, v)
+        res.append(("adam_3steps(n=%d)" % n, _err(pd, p64), 1e-6))
+        res.append(("adam_3steps_update(n=%d)" % n, _err(pd - p0.to(DEV), p64 - p0.double()), 2e-3))
+        res.append(("adam_dev_bitwise(n=%d)" % n, float(not same), 0.0))
+        res.append(("adam_dev_count(n=%d)" % n, float(float(state[0]) != 3.0 or float(state[1]) != lrs[2]), 0.0))
+    return res
+
+
+def check_sum_slabs():
+    """ops.sum_slabs (optim.FlatAdam's fold of the per-use gradient slabs): 1..4 slabs, lengths around the float4 width,
+    every operand starting on a 16-byte boundary (the float4 path) or one element behind it (the scalar path) — bit for
+    bit the fp32 sum in the kernel's order (((g + s0) + s1) + s2) + s3"""
+    from sivae_hip import ops
+    res = []
+    for n in (1, 3, 4, 1027):
+        for start in (0, 1):
+            for k in (1, 2, 3, 4):
+                host = [_rand(n + 1, seed=20 + i).float() for i in range(k + 1)]
+                base = [t.to(DEV) for t in host]
+                want = host[0][start:start + n].clone()
+                for t in host[1:]:
+                    want = want + t[start:start + n]
+                g = base[0][start:start + n]
+                ops.sum_slabs(g, [t[start:start + n] for t in base[1:]])
+                ok = torch.equal(g.cpu(), want)
+                # the element on the other side of the slice belongs to a neighbour: untouched
+                other = n if start == 0 else 0
+                ok = ok and all(float(b[other]) == float(h[other]) for b, h in zip(base, host))
+                res.append(("sum_slabs(n=%d,start=%d,slabs=%d)" % (n, start, k), float(not ok), 0.0))
+    return res
 
 
 def check_bn_apply_resup():
@@ -1749,6 +1825,7 @@ def all_checks():
     checks.append(("adversarial", check_adversarial))
     checks.append(("randn", check_randn))
     checks.append(("adam", check_adam))
+    checks.append(("sum_slabs", check_sum_slabs))
     return checks
 
 
