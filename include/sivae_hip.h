@@ -684,6 +684,20 @@ int sivae_relu_bn_bwd(const float* dy, const float* a, const float* mean, const 
  * (lowest index on a tie); _bwd writes g [B][C] at the argmax of an otherwise zero dx [B][C][N] in one kernel. */
 int sivae_max_points_fwd(const float* x, float* vals, int* arg, int B, int C, int N, sivae_stream_t stream);
 int sivae_max_points_bwd(const float* g, const int* arg, float* dx, int B, int C, int N, sivae_stream_t stream);
+/* The encoder's last stage in one piece: max over the points of BatchNorm1d(ReLU(a)), a [B][C][N], without y or the max's
+ * dense gradient in memory.  _fwd: mean / invstd from sivae_relu_bn_stats (eval mode: the running mean and
+ * rsqrt(running_var + eps)); y = relu(a) * (gamma invstd) + (beta - mean gamma invstd) is formed in registers with
+ * sivae_relu_bn_apply's operations, so vals [B][C] and the int32 arg [B][C] are bit-identical to
+ * sivae_max_points_fwd(sivae_relu_bn_apply(a)): a NaN is the maximum, the lowest index wins among ties and among NaNs.
+ * _bwd: from g [B][C] and the forward's arg.  dy is g at arg and zero elsewhere, so dbeta = sum_b g and
+ * dgamma = invstd (sum_b g relu(a[b][c][arg]) - mean dbeta) are sums over B values per channel (fp64, fixed order; arg is
+ * clamped into the row), then one pass reads a and writes da = [a > 0] gamma invstd (dy - dbeta / m - rhat dgamma / m),
+ * m = B N.  No workspace, no atomics; 16-byte accesses when N % 4 == 0 and a (and da) are 16-byte aligned. */
+int sivae_relu_bn_max_fwd(const float* a, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                          float* vals, int* arg, int B, int C, int N, sivae_stream_t stream);
+int sivae_relu_bn_max_bwd(const float* g, const int* arg, const float* a, const float* mean, const float* invstd,
+                          const float* gamma, float* da, float* dgamma, float* dbeta, int B, int C, int N,
+                          sivae_stream_t stream);
 
 /* ---- point clouds: the JSD validation metric (pc_jsd.hip) ----------------------------------------------------------
  * _entropy_of_occupancy_grid (soft_intro_vae_3d/metrics/jsd.py:97-126, the NearestNeighbors fit and the per-point Python

@@ -508,3 +508,138 @@ extern "C" int sivae_max_points_bwd(const float* g, const int* arg, float* dx, i
     hipLaunchKernelGGL((max_points_bwd_kernel<false>), dim3(cdiv(total, PC_NT)), dim3(PC_NT), 0, stream, g, arg, dx, N, total);
   return sivae_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------ ReLU -> BatchNorm1d -> max
+// The encoder's last stage: y = BatchNorm1d(ReLU(a)) is only ever looked at through its max over the points, so neither y
+// nor the max's dense gradient has to exist.  Forward: max_points_fwd_kernel's walk with relu_bn_apply_kernel<., false>'s
+// expression formed in registers in front of it (the same operations on the same values: vals and arg are the
+// composition's, bit for bit); nothing of size B C N is written.  The statistics stay sivae_relu_bn_stats.
+template <bool VEC>
+__global__ void __launch_bounds__(PC_NT) relu_bn_max_fwd_kernel(const float* __restrict__ a, const float* __restrict__ mean,
+                                                                const float* __restrict__ invstd,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                float* __restrict__ vals, int* __restrict__ arg, int rows,
+                                                                int C, int N) {
+  const int row = blockIdx.x * (PC_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;  // (wave-uniform)
+  const int c = row % C;
+  const float mu = mean[c], is = invstd[c], ga = gamma[c];
+  const float sc = ga * is, sh = beta[c] - mu * sc;
+  const float* p = a + (size_t)row * N;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  if (VEC) {
+    for (int i = lane * 4; i < N; i += 256) {
+      const float4 v = *reinterpret_cast<const float4*>(p + i);
+      max_walk(bv, bi, relu0(v.x) * sc + sh, i);
+      max_walk(bv, bi, relu0(v.y) * sc + sh, i + 1);
+      max_walk(bv, bi, relu0(v.z) * sc + sh, i + 2);
+      max_walk(bv, bi, relu0(v.w) * sc + sh, i + 3);
+    }
+  } else {
+    for (int i = lane; i < N; i += 64) max_walk(bv, bi, relu0(p[i]) * sc + sh, i);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    max_take(bv, bi, ov, oi);
+  }
+  if (lane == 0) {
+    vals[row] = bv;
+    arg[row] = bi < N ? bi : 0;  // (a row of -inf only: no lane took an element; index 0)
+  }
+}
+
+// Backward, first launch.  The max's gradient dy is g[b][c] at arg[b][c] and zero elsewhere, so BatchNorm's two sums over
+// a channel's B N values are sums over B elements: sum dy = sum_b g, sum dy r = sum_b g relu(a[b][c][arg]).  One wave
+// per channel, lane l takes b = l, l + 64, ... in fp64, then the butterfly: a fixed order, two runs are bit-identical.
+// The formulas are relu_bn_bwd_finalize_kernel's.
+__global__ void __launch_bounds__(PC_NT) relu_bn_max_bwd_sums_kernel(const float* __restrict__ g, const int* __restrict__ arg,
+                                                                     const float* __restrict__ a,
+                                                                     const float* __restrict__ mean,
+                                                                     const float* __restrict__ invstd,
+                                                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                     int B, int C, int N) {
+  const int c = blockIdx.x * (PC_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;  // (wave-uniform)
+  double sdy = 0.0, sdyr = 0.0;
+  for (int b = lane; b < B; b += 64) {
+    const size_t row = (size_t)b * C + c;
+    const int k = min(max(arg[row], 0), N - 1);  // (an index array from elsewhere must not make this read leave the row)
+    const float gv = g[row], r = relu0(a[row * N + k]);
+    sdy += (double)gv;
+    sdyr += (double)gv * r;
+  }
+  sdy = wave_sum(sdy);
+  sdyr = wave_sum(sdyr);
+  if (lane == 0) {
+    dbeta[c] = (float)sdy;
+    dgamma[c] = (float)((double)invstd[c] * (sdyr - (double)mean[c] * sdy));
+  }
+}
+
+// Backward, second launch: relu_bn_apply_kernel<., true>'s expression with dy synthesised from (g, arg) — one read of a,
+// one write of da.  The store is the last thing a thread does (the store-data note in common.h).
+template <bool VEC>
+__global__ void __launch_bounds__(PC_NT) relu_bn_max_bwd_apply_kernel(const float* __restrict__ a, const float* __restrict__ g,
+                                                                      const int* __restrict__ arg,
+                                                                      const float* __restrict__ mean,
+                                                                      const float* __restrict__ invstd,
+                                                                      const float* __restrict__ gamma,
+                                                                      const float* __restrict__ dgamma,
+                                                                      const float* __restrict__ dbeta, float* __restrict__ da,
+                                                                      int C, int N, size_t total, float inv_m) {
+  const size_t e = ((size_t)blockIdx.x * PC_NT + threadIdx.x) * (VEC ? 4 : 1);
+  if (e >= total) return;
+  const size_t row = e / (size_t)N;
+  const int c = (int)(row % (size_t)C), i = (int)(e - row * (size_t)N), kk = arg[row];
+  const float gv = g[row];
+  const float mu = mean[c], is = invstd[c], ga = gamma[c];
+  const float k = ga * is, mb = dbeta[c] * inv_m, mg = dgamma[c] * inv_m;
+#define PC_DA(A, G) ((A) > 0.f ? k * ((G) - mb - ((A) - mu) * is * mg) : 0.f)
+  if (VEC) {
+    const float4 v = *reinterpret_cast<const float4*>(a + e);
+    *reinterpret_cast<float4*>(da + e) =
+        make_float4(PC_DA(v.x, i == kk ? gv : 0.f), PC_DA(v.y, i + 1 == kk ? gv : 0.f), PC_DA(v.z, i + 2 == kk ? gv : 0.f),
+                    PC_DA(v.w, i + 3 == kk ? gv : 0.f));
+  } else {
+    const float v = a[e];
+    da[e] = PC_DA(v, i == kk ? gv : 0.f);
+  }
+#undef PC_DA
+}
+
+extern "C" int sivae_relu_bn_max_fwd(const float* a, const float* mean, const float* invstd, const float* gamma,
+                                     const float* beta, float* vals, int* arg, int B, int C, int N, hipStream_t stream) {
+  if (!a || !mean || !invstd || !gamma || !beta || !vals || !arg) return SIVAE_ERR_NULL;
+  const int rc = relu_bn_check(B, C, N);
+  if (rc != SIVAE_OK) return rc;
+  const int rows = B * C;
+  if ((N & 3) == 0 && pc_aligned16(a))
+    hipLaunchKernelGGL((relu_bn_max_fwd_kernel<true>), dim3(cdiv(rows, PC_NT / 64)), dim3(PC_NT), 0, stream, a, mean, invstd,
+                       gamma, beta, vals, arg, rows, C, N);
+  else
+    hipLaunchKernelGGL((relu_bn_max_fwd_kernel<false>), dim3(cdiv(rows, PC_NT / 64)), dim3(PC_NT), 0, stream, a, mean, invstd,
+                       gamma, beta, vals, arg, rows, C, N);
+  return sivae_launch_status();
+}
+
+extern "C" int sivae_relu_bn_max_bwd(const float* g, const int* arg, const float* a, const float* mean, const float* invstd,
+                                     const float* gamma, float* da, float* dgamma, float* dbeta, int B, int C, int N,
+                                     hipStream_t stream) {
+  if (!g || !arg || !a || !mean || !invstd || !gamma || !da || !dgamma || !dbeta) return SIVAE_ERR_NULL;
+  const int rc = relu_bn_check(B, C, N);
+  if (rc != SIVAE_OK) return rc;
+  const size_t total = (size_t)B * C * N;
+  const float inv_m = (float)(1.0 / (double)((long long)B * N));
+  hipLaunchKernelGGL(relu_bn_max_bwd_sums_kernel, dim3(cdiv(C, PC_NT / 64)), dim3(PC_NT), 0, stream, g, arg, a, mean, invstd,
+                     dgamma, dbeta, B, C, N);
+  if ((N & 3) == 0 && pc_aligned16(a) && pc_aligned16(da))
+    hipLaunchKernelGGL((relu_bn_max_bwd_apply_kernel<true>), dim3(cdiv(total / 4, PC_NT)), dim3(PC_NT), 0, stream, a, g, arg,
+                       mean, invstd, gamma, (const float*)dgamma, (const float*)dbeta, da, C, N, total, inv_m);
+  else
+    hipLaunchKernelGGL((relu_bn_max_bwd_apply_kernel<false>), dim3(cdiv(total, PC_NT)), dim3(PC_NT), 0, stream, a, g, arg, mean,
+                       invstd, gamma, (const float*)dgamma, (const float*)dbeta, da, C, N, total, inv_m);
+  return sivae_launch_status();
+}

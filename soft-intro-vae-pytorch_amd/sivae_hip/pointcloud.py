@@ -4,6 +4,9 @@ csrc/pointcloud.hip: tensor-level wrappers in the style of `ops` and the autogra
   chamfer_distance(preds [B, M, 3], gts [B, N, 3]) -> [B]       losses/chamfer_loss.py:11-17 (direct-form distances)
   relu_bn(a [B, C, N], weight, bias, BNState)      -> [B, C, N]  nn.ReLU -> nn.BatchNorm1d, relu(a) never stored
   max_points(y [B, C, N])                          -> [B, C]     y.max(dim=2)[0]
+  relu_bn_max(a [B, C, N], weight, bias, BNState)  -> [B, C]     max_points(relu_bn(a)) in one piece: neither y nor the
+                                                                 max's dense gradient is stored (RELU_BN_MAX: the encoder
+                                                                 uses it for its last stage)
   pointwise_conv(x [B, Ci, N], w [Co, Ci, 1], bias, relu=False)  nn.Conv1d(kernel_size=1) on the ks = 1 conv kernels
 
 and the validation metric (metrics/jsd.py) on the kernels of csrc/pc_jsd.hip, not differentiable:
@@ -24,6 +27,8 @@ from . import ops
 from .ops import _p, _require, _s, timer_begin, timer_end, workspace
 
 BN_EVAL_BWD_MSG = "sivae_hip: backward through eval-mode BatchNorm is not supported"  # (the image blocks' message)
+# models/vae.py::Encoder sends its last ReLU -> BatchNorm1d -> max stage through relu_bn_max (same values, bit for bit)
+RELU_BN_MAX = True
 
 
 def _require_i32(*tensors):
@@ -149,6 +154,39 @@ def max_points_bwd(g, arg, N):
     dx = torch.empty((B, C, N), dtype=torch.float32, device=g.device)
     _lib.call("sivae_max_points_bwd", _p(g), _p(arg), _p(dx), B, C, N, _s(g))
     return dx
+
+
+def relu_bn_max_fwd(a, mean, invstd, gamma, beta):
+    """max over the points of relu_bn_apply(a, ...) without storing it -> (values [B, C], int32 argmax [B, C]), bit-identical
+    to max_points_fwd(relu_bn_apply(a, mean, invstd, gamma, beta))"""
+    _require_f32(a, mean, invstd, gamma, beta)
+    B, C, N = _bcn(a)
+    vals = torch.empty((B, C), dtype=torch.float32, device=a.device)
+    arg = torch.empty((B, C), dtype=torch.int32, device=a.device)
+    t0 = timer_begin()
+    _lib.call("sivae_relu_bn_max_fwd", _p(a), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(vals), _p(arg), B, C, N, _s(a))
+    if t0 is not None:
+        timer_end(t0, "relu_bn_max_fwd_kernel", 7.0 * a.numel())
+    return vals, arg
+
+
+def relu_bn_max_bwd(g, arg, a, mean, invstd, gamma):
+    """-> (da, dgamma, dbeta) from the upstream gradient g [B, C] and the forward's arg: the max's gradient is g at arg and
+    zero elsewhere, never stored"""
+    _require_f32(g, a, mean, invstd, gamma)
+    _require_i32(arg)
+    B, C, N = _bcn(a)
+    if tuple(g.shape) != (B, C) or tuple(arg.shape) != (B, C):
+        raise ValueError("sivae_hip.relu_bn_max_bwd: g and arg [B, C] expected for a [B, C, N]")
+    da = torch.empty_like(a)
+    dgamma = torch.empty(C, dtype=torch.float32, device=a.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=a.device)
+    t0 = timer_begin()
+    _lib.call("sivae_relu_bn_max_bwd", _p(g), _p(arg), _p(a), _p(mean), _p(invstd), _p(gamma), _p(da), _p(dgamma), _p(dbeta),
+              B, C, N, _s(a))
+    if t0 is not None:
+        timer_end(t0, "relu_bn_max_bwd", 8.0 * a.numel())
+    return da, dgamma, dbeta
 
 
 # ------------------------------------------------------------------------------------------------ the JSD metric
@@ -339,6 +377,36 @@ class MaxPointsFn(torch.autograd.Function):
 
 def max_points(y):
     return MaxPointsFn.apply(y)
+
+
+class ReluBnMaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, weight, bias, st):
+        a = a.contiguous()
+        if st.training:
+            mean, invstd = relu_bn_stats(a, st.running_mean, st.running_var, st.num_batches_tracked, st.eps,
+                                         st.momentum if st.momentum is not None else 0.1)
+        else:
+            mean, invstd = st.running_mean, torch.rsqrt(st.running_var + st.eps)
+        vals, arg = relu_bn_max_fwd(a, mean, invstd, weight.detach(), bias.detach())
+        ctx.training = st.training
+        ctx.save_for_backward(a, mean, invstd, weight, arg)
+        return vals
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.training:
+            raise RuntimeError(BN_EVAL_BWD_MSG)
+        a, mean, invstd, weight, arg = ctx.saved_tensors
+        da, dgamma, dbeta = relu_bn_max_bwd(g.contiguous(), arg, a, mean, invstd, weight.detach())
+        return da, dgamma, dbeta, None
+
+
+def relu_bn_max(a, weight, bias, st):
+    """max_points(relu_bn(a, weight, bias, st)) -> [B, C], the same values and buffer updates, in two tensor passes forward
+    and two backward"""
+    _bcn(a)  # (the shape error before anything else: a 2-D input would otherwise reach the statistics first)
+    return ReluBnMaxFn.apply(a, weight, bias, st)
 
 
 def _pack1(w, mode):

@@ -107,6 +107,8 @@ class Encoder(nn.Module):
         for i in range(0, len(mods), 3):
             bn = mods[i + 2]
             a = PC.pointwise_conv(x, mods[i].weight, None)
+            if i + 3 == len(mods) and PC.RELU_BN_MAX:  # (the last stage and the max in one piece: y is never stored)
+                return _heads(self, PC.relu_bn_max(a, bn.weight, bn.bias, SF.BNState(bn)))
             x = PC.relu_bn(a, bn.weight, bn.bias, SF.BNState(bn))
         return _heads(self, PC.max_points(x))
 
