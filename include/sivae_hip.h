@@ -725,6 +725,30 @@ int sivae_voxel_histogram(const float* pc, long long stride_s, long long stride_
 int sivae_js_divergence(const void* P, const void* Q, int p_is_f64, int q_is_f64, int n, double* out,
                         sivae_stream_t stream);
 
+/* ---- point clouds: minimum matching distance and coverage (pc_eval.hip) -------------------------------------------
+ * What soft_intro_vae_3d/README.md:47-48 asks for after evaluation/generate_data_for_metrics.py has saved its arrays: the
+ * all-pairs Chamfer matrix of two sets of clouds.  sample: S clouds of M points, ref: R clouds of N points, each read in
+ * place through three ELEMENT strides (cloud, point, coordinate) as sivae_occupancy_grid reads its clouds.  With
+ * a_j = min_i |P_j - Q_i|^2 and b_i = min_j |P_j - Q_i|^2 (direct form dx^2 + dy^2 + dz^2, fp32),
+ *   D[s][r] = sum_j f(a_j) / m + sum_i f(b_i) / n,   f(t) = t or sqrt(t) (use_sqrt), m = M, n = N (normalize) or 1,
+ * float32 [S][R]; one call writes the rows s0 <= s < s1 (the caller bounds the length of one launch with the range).
+ * Every distance is computed once and serves both minima; no nearest-neighbour indices.  The sums are taken in fp64 in a
+ * fixed order: two runs are bit-identical.  A cloud with a NaN or infinite coordinate makes every entry of its row or
+ * column non-finite and changes no other entry.  Any M, N >= 1; SIVAE_ERR_RANGE for S R >= 2^31 - 1; SIVAE_ERR_SHAPE for
+ * an empty or out-of-range row range; SIVAE_ERR_MODE for a flag that is not 0 or 1.  The workspace (sized for s1 - s0
+ * rows) is only used when M > 2048 and N > 2048; its size is 0 otherwise, the pointer must still not be NULL. */
+size_t sivae_chamfer_matrix_workspace_bytes(int rows, int R, int M, int N);
+int sivae_chamfer_matrix(const float* sample, long long sample_stride_s, long long sample_stride_n,
+                         long long sample_stride_c, const float* ref, long long ref_stride_s, long long ref_stride_n,
+                         long long ref_stride_c, float* D, int S, int R, int M, int N, int s0, int s1, int normalize,
+                         int use_sqrt, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+/* Row and column minima of a contiguous float32 D [S][R] in one launch: row_min / row_arg [S] (the coverage side:
+ * the reference cloud each sample matches), col_min / col_arg [R] (the minimum-matching-distance side).  int32 indices,
+ * the lowest index wins a tie; +inf and NaN entries never win, and a row or column without any other entry yields
+ * (+inf, 0).  SIVAE_ERR_RANGE for S R >= 2^31 - 1. */
+int sivae_match_min(const float* D, int S, int R, float* row_min, int* row_arg, float* col_min, int* col_arg,
+                    sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,12 @@ and the validation metric (metrics/jsd.py) on the kernels of csrc/pc_jsd.hip, no
   voxel_histogram(pc [S, N, 3], n_voxels)                    -> counts int32 [n_voxels^3]
   js_divergence(P, Q)                                        -> 0-dim float64 tensor
 
+and the set-to-set evaluation (metrics/evaluation_metrics.py: minimum matching distance, coverage) on the kernels of
+csrc/pc_eval.hip, not differentiable:
+
+  chamfer_matrix(sample [S, M, 3], ref [R, N, 3], normalize=True, use_sqrt=False) -> D [S, R], D[s, r] = CD(sample_s, ref_r)
+  match_min(D [S, R])                                        -> (row_min [S], row_arg int32 [S], col_min [R], col_arg int32 [R])
+
 The pointwise convolutions and the MLPs run on what exists (`ops.conv2d_fwd` / `conv2d_wgrad` with ks = 1, `SF.linear`).
 There is no CPU path: a CPU tensor raises the engine's usual message.
 """
@@ -306,6 +312,60 @@ def js_divergence(P, Q):
     if t0 is not None:
         timer_end(t0, "js_divergence_kernel", 12.0 * P.numel())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ MMD-CD / COV-CD
+# Point pairs (rows x R x M x N) one launch of chamfer_matrix may cover: the rows of D are walked in slabs of at least one
+# row so that a launch stays short on a device other work shares.
+# Measured on an MI355X (tools/bench_pc_eval.py, profiles/pc_eval_bench.txt): 2400 x 800 clouds of 2048 points are 60
+# launches of 40 rows, the longest 21.6 ms (the first), the others 18.6 - 19.0 ms.
+MATRIX_POINT_PAIRS_PER_LAUNCH = 1 << 37
+
+
+def chamfer_matrix(sample, ref, normalize=True, use_sqrt=False):
+    """All-pairs Chamfer distance of two sets of clouds, sample [S, M, 3] and ref [R, N, 3] (float32, any strides: the
+    `transpose(1, 2)` view of a [S, 3, M] decoder output is read in place) -> D [S, R] float32 with
+    D[s, r] = sum_j f(min_i |P_j - Q_i|^2) / m + sum_i f(min_j |P_j - Q_i|^2) / n, f = sqrt when use_sqrt, m = M and n = N
+    when normalize (1 otherwise).  A cloud with a non-finite coordinate makes its row / column of D non-finite."""
+    for pcs in (sample, ref):  # (the shape error before the device's, as relu_bn_max does)
+        if pcs.dim() != 3 or pcs.shape[2] != 3:
+            raise ValueError("sivae_hip.chamfer_matrix: expected point clouds [S, N, 3], got %s" % (tuple(pcs.shape),))
+    S, M, sa = _require_clouds(sample, "chamfer_matrix")
+    R, N, sb = _require_clouds(ref, "chamfer_matrix")
+    if sample.device != ref.device:
+        raise ValueError("sivae_hip.chamfer_matrix: sample is on %s, ref on %s" % (sample.device, ref.device))
+    if S * R >= 0x7fffffff:
+        raise ValueError("sivae_hip.chamfer_matrix: %d x %d cloud pairs do not fit an int32 index" % (S, R))
+    D = torch.empty((S, R), dtype=torch.float32, device=sample.device)
+    slab = max(1, min(S, MATRIX_POINT_PAIRS_PER_LAUNCH // (R * M * N)))
+    ws = workspace(_lib.load().sivae_chamfer_matrix_workspace_bytes(slab, R, M, N), sample.device)
+    for s0 in range(0, S, slab):
+        s1 = min(S, s0 + slab)
+        t0 = timer_begin()
+        _lib.call("sivae_chamfer_matrix", _p(sample), sa[0], sa[1], sa[2], _p(ref), sb[0], sb[1], sb[2], _p(D), S, R, M, N,
+                  s0, s1, int(bool(normalize)), int(bool(use_sqrt)), _p(ws), ws.numel(), _s(sample))
+        if t0 is not None:
+            # per point pair: 3 subtractions, a multiply and 2 FMAs, the row minimum and a share of the column minimum
+            timer_end(t0, "chamfer_matrix_kernel", 8.0 * (s1 - s0) * R * M * N)
+    return D
+
+
+def match_min(D):
+    """D [S, R] float32 -> (row_min [S], row_arg int32 [S], col_min [R], col_arg int32 [R]); the lowest index wins a tie,
+    +inf / NaN entries never win, a row or column of nothing else gives (+inf, 0)"""
+    if D.dim() != 2 or D.shape[0] == 0 or D.shape[1] == 0:
+        raise ValueError("sivae_hip.match_min: expected a matrix [S, R], got %s" % (tuple(D.shape),))
+    _require_f32(D)
+    S, R = D.shape
+    row_min = torch.empty(S, dtype=torch.float32, device=D.device)
+    row_arg = torch.empty(S, dtype=torch.int32, device=D.device)
+    col_min = torch.empty(R, dtype=torch.float32, device=D.device)
+    col_arg = torch.empty(R, dtype=torch.int32, device=D.device)
+    t0 = timer_begin()
+    _lib.call("sivae_match_min", _p(D), S, R, _p(row_min), _p(row_arg), _p(col_min), _p(col_arg), _s(D))
+    if t0 is not None:
+        timer_end(t0, "match_min_kernel", 4.0 * S * R)
+    return row_min, row_arg, col_min, col_arg
 
 
 # ------------------------------------------------------------------------------------------------ autograd
