@@ -749,6 +749,35 @@ int sivae_chamfer_matrix(const float* sample, long long sample_stride_s, long lo
 int sivae_match_min(const float* D, int S, int R, float* row_min, int* row_arg, float* col_min, int* col_arg,
                     sivae_stream_t stream);
 
+/* ---- point clouds: the earth mover's distance matrix (pc_emd.hip) --------------------------------------------------
+ * MMD-EMD / COV-EMD, the two remaining figures of the tables soft_intro_vae_3d/README.md:47-48 points to (the notebook's
+ * minimum_mathing_distance / coverage with use_EMD): the all-pairs matrix of the APPROXIMATE-MATCHING earth mover's
+ * distance of Fan, Su and Guibas ("A point set generation network for 3D object reconstruction from a single image",
+ * CVPR 2017; the approxmatch / matchcost pair).  For a left cloud A [n][3] and a right cloud B [m][3], with
+ * d2(k, l) = |A_k - B_l|^2 in the direct form (fp32):
+ *   big = max(n, m);  remL[k] = big / n;  remR[l] = big / m   (real division; the original divides as integers, which
+ *   cost = 0                                                   is the same for n = m)
+ *   for j = 7, 6, ..., -2:   level = -4^j, and 0 at j = -2;   w(k, l) = exp(level d2(k, l))
+ *     1. suml[k] = 1e-9 + sum_l w(k, l) remR[l];   ratioL[k] = remL[k] / suml[k]
+ *     2. sumr[l] = remR[l] sum_k w(k, l) ratioL[k];   ratioR[l] = remR[l] min(remR[l] / (sumr[l] + 1e-9), 1);
+ *        remR[l] = max(0, remR[l] - sumr[l])
+ *     3. t(k, l) = w(k, l) ratioL[k] ratioR[l];   cost += sum_kl t(k, l) sqrt(d2(k, l));
+ *        remL[k] = max(0, remL[k] - sum_l t(k, l))
+ *   EMD(A, B) = cost / big (normalize) or cost.
+ * D[s][r] = EMD(left = ref_r, right = sample_s), float32 [S][R]; the quantity is not symmetric.  Arguments, strides, the
+ * row range s0 <= s < s1 and the return codes are sivae_chamfer_matrix's.  The weights are exp2 of level log2(e) d2 (the
+ * hardware's exponential), d2 is recomputed in each of the thirty sweeps.  Every per-point sum of a level is fp32 in index
+ * order, the cost's included (sum_l t sqrt(d2) of one left point, up to 4096 terms); those per-point, per-level costs are
+ * added in fp64 in a fixed order: D does not depend on the grid, the row range, the strides or the run.  A cloud
+ * with a NaN or infinite coordinate makes every entry of its row or column NaN (found while loading) and changes no other
+ * entry.  1 <= M, N <= 4096 (both clouds are held in LDS); SIVAE_ERR_RANGE beyond, and for S R >= 2^31 - 1.  No
+ * workspace is used: the size is 0, the pointer must still not be NULL. */
+size_t sivae_emd_matrix_workspace_bytes(int rows, int R, int M, int N);
+int sivae_emd_matrix(const float* sample, long long sample_stride_s, long long sample_stride_n, long long sample_stride_c,
+                     const float* ref, long long ref_stride_s, long long ref_stride_n, long long ref_stride_c, float* D,
+                     int S, int R, int M, int N, int s0, int s1, int normalize, void* workspace, size_t workspace_bytes,
+                     sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ csrc/pc_eval.hip, not differentiable:
 
   chamfer_matrix(sample [S, M, 3], ref [R, N, 3], normalize=True, use_sqrt=False) -> D [S, R], D[s, r] = CD(sample_s, ref_r)
   match_min(D [S, R])                                        -> (row_min [S], row_arg int32 [S], col_min [R], col_arg int32 [R])
+  emd_matrix(sample [S, M, 3], ref [R, N, 3], normalize=True) -> D [S, R], D[s, r] = EMD(left = ref_r, right = sample_s)  (csrc/pc_emd.hip)
 
 The pointwise convolutions and the MLPs run on what exists (`ops.conv2d_fwd` / `conv2d_wgrad` with ks = 1, `SF.linear`).
 There is no CPU path: a CPU tensor raises the engine's usual message.
@@ -366,6 +367,56 @@ def match_min(D):
     if t0 is not None:
         timer_end(t0, "match_min_kernel", 4.0 * S * R)
     return row_min, row_arg, col_min, col_arg
+
+
+# ------------------------------------------------------------------------------------------------ MMD-EMD / COV-EMD
+EMD_MAX_POINTS = 4096  # (both clouds of a pair are held in LDS)
+# Point pairs (cloud pairs x M x N) one launch of emd_matrix may cover, as MATRIX_POINT_PAIRS_PER_LAUNCH above; a point pair
+# is visited in thirty sweeps with an exponential each, against once for the Chamfer matrix.  A row of D longer than that
+# goes in blocks of columns.  2^31 is 512 cloud pairs of 2048 points: one block per pair, two resident blocks on each of
+# the 256 compute units, so a launch is one round of them.
+# Measured on an MI355X (tools/bench_pc_emd.py, profiles/pc_emd_bench.txt), clouds of 2048 points: launches of
+# 512 cloud pairs take 14.1 - 14.3 ms (64 x 64 clouds, 40 launches); 2400 x 800 clouds are 4800 launches of 512 and 288
+# pairs, the longest 16.1 ms, the median 15.0 ms.  One whole row of 800 pairs in a launch took 28.9 ms.
+EMD_POINT_PAIRS_PER_LAUNCH = 1 << 31
+
+
+def emd_matrix(sample, ref, normalize=True):
+    """All-pairs approximate-matching earth mover's distance (Fan, Su, Guibas; include/sivae_hip.h states the ten levels)
+    of two sets of clouds, sample [S, M, 3] and ref [R, N, 3] (float32, any strides, at most 4096 points a cloud)
+    -> D [S, R] float32 with D[s, r] = EMD(left = ref_r, right = sample_s): the cost of the matching, divided by
+    max(M, N) when normalize.  Not symmetric in its arguments.  A cloud with a non-finite coordinate makes its row /
+    column of D NaN."""
+    for pcs in (sample, ref):  # (the shape error before the device's, as chamfer_matrix does)
+        if pcs.dim() != 3 or pcs.shape[2] != 3:
+            raise ValueError("sivae_hip.emd_matrix: expected point clouds [S, N, 3], got %s" % (tuple(pcs.shape),))
+    S, M, sa = _require_clouds(sample, "emd_matrix")
+    R, N, sb = _require_clouds(ref, "emd_matrix")
+    if sample.device != ref.device:
+        raise ValueError("sivae_hip.emd_matrix: sample is on %s, ref on %s" % (sample.device, ref.device))
+    if M > EMD_MAX_POINTS or N > EMD_MAX_POINTS:
+        raise ValueError("sivae_hip.emd_matrix: clouds of %d and %d points, at most %d are supported" % (M, N, EMD_MAX_POINTS))
+    if S * R >= 0x7fffffff:
+        raise ValueError("sivae_hip.emd_matrix: %d x %d cloud pairs do not fit an int32 index" % (S, R))
+    D = torch.empty((S, R), dtype=torch.float32, device=sample.device)
+    pairs = max(1, EMD_POINT_PAIRS_PER_LAUNCH // (M * N))    # cloud pairs one launch may cover:
+    rows, cols = max(1, min(S, pairs // R)), min(R, pairs)   # a slab of whole rows, or ONE row in blocks of columns
+    ws = workspace(_lib.load().sivae_emd_matrix_workspace_bytes(rows, cols, M, N), sample.device)
+    for s0 in range(0, S, rows):
+        s1 = min(S, s0 + rows)
+        for r0 in range(0, R, cols):
+            r1 = min(R, r0 + cols)
+            # D[s0:s1, r0:r1] (whole rows, or a stretch of one) is contiguous: to the library it is the whole matrix of
+            # sample[s0:s1] against ref[r0:r1]; an entry does not depend on which launch computes it
+            t0 = timer_begin()
+            _lib.call("sivae_emd_matrix", _p(sample[s0:s1]), sa[0], sa[1], sa[2], _p(ref[r0:r1]), sb[0], sb[1], sb[2],
+                      _p(D[s0:s1, r0:r1]), s1 - s0, r1 - r0, M, N, 0, s1 - s0, int(bool(normalize)), _p(ws), ws.numel(),
+                      _s(sample))
+            if t0 is not None:
+                # per point pair and sweep: the distance (6), its scaling, the exponential and the sum (9); the third
+                # sweep of a level adds the root and the cost (12)
+                timer_end(t0, "emd_matrix_kernel", 300.0 * (s1 - s0) * (r1 - r0) * M * N)
+    return D
 
 
 # ------------------------------------------------------------------------------------------------ autograd

@@ -1,14 +1,15 @@
-"""Minimum matching distance and coverage of two sets of point clouds, Chamfer variant (MMD-CD, COV-CD): the two figures
-the reference's README (soft_intro_vae_3d/README.md:47-48) sends the arrays of evaluation/generate_data_for_metrics.py to
-the latent_3d_points evaluation notebook for.  The function names, signatures and return types are that notebook's
-(`minimum_mathing_distance` is its spelling); the work runs on the kernels of csrc/pc_eval.hip through
-`sivae_hip.pointcloud`.  Inputs are ROCm tensors, CPU tensors or numpy arrays [S, N, 3]; host data is uploaded once.  No
-TensorFlow session (`sess`, `batch_size` and `verbose` are accepted and ignored: the whole matrix is one walk over the
-rows on the device).
+"""Minimum matching distance and coverage of two sets of point clouds, on a Chamfer matrix (MMD-CD, COV-CD) or an earth
+mover's matrix (MMD-EMD, COV-EMD): the figures the reference's README (soft_intro_vae_3d/README.md:47-48) sends the arrays
+of evaluation/generate_data_for_metrics.py to the latent_3d_points evaluation notebook for.  The function names,
+signatures and return types are that notebook's (`minimum_mathing_distance` is its spelling); the work runs on the kernels
+of csrc/pc_eval.hip and csrc/pc_emd.hip through `sivae_hip.pointcloud`.  Inputs are ROCm tensors, CPU tensors or numpy
+arrays [S, N, 3]; host data is uploaded once.  No TensorFlow session (`sess`, `batch_size` and `verbose` are accepted and
+ignored: the whole matrix is one walk over the rows on the device).
 
     D = chamfer_matrix(sample_pcs, ref_pcs)               # pay for the matrix once ...
     mmd, matched_dists = minimum_mathing_distance(sample_pcs, ref_pcs, dist=D)
     cov, matched_ref = coverage(sample_pcs, ref_pcs, dist=D)
+    mmd_emd, _ = minimum_mathing_distance(x_g, x, dist=emd_matrix(x_g, x))   # the earth mover's figures: the same calls
 """
 import os
 import sys
@@ -21,7 +22,7 @@ if _PKG not in sys.path:
     sys.path.append(_PKG)
 from sivae_hip import pointcloud as PC  # noqa: E402
 
-__all__ = ['chamfer_matrix', 'minimum_mathing_distance', 'minimum_matching_distance', 'coverage']
+__all__ = ['chamfer_matrix', 'emd_matrix', 'minimum_mathing_distance', 'minimum_matching_distance', 'coverage']
 
 
 def _device_of(*arrays):
@@ -54,9 +55,21 @@ def chamfer_matrix(sample_pcs, ref_pcs, normalize=True, use_sqrt=False):
     return PC.chamfer_matrix(_clouds(sample_pcs, dev, "sample_pcs"), _clouds(ref_pcs, dev, "ref_pcs"), normalize, use_sqrt)
 
 
+def emd_matrix(sample_pcs, ref_pcs, normalize=True):
+    """D [S, R] float32 on the device, D[s, r] = EMD(ref_r, sample_s): the cost of the approximate matching (the notebook's
+    approxmatch / matchcost pair) of the two clouds, divided by the larger point count with `normalize`.  At most 4096
+    points a cloud.  `dist=` of the two functions below takes it: MMD-EMD and COV-EMD."""
+    for name, pcs in (("sample_pcs", sample_pcs), ("ref_pcs", ref_pcs)):  # (the shape error before any device is asked for)
+        if np.ndim(pcs) != 3 or np.shape(pcs)[2] != 3:
+            raise ValueError("%s: expected point clouds [S, N, 3], got %s" % (name, tuple(np.shape(pcs))))
+    dev = _device_of(sample_pcs, ref_pcs)
+    return PC.emd_matrix(_clouds(sample_pcs, dev, "sample_pcs"), _clouds(ref_pcs, dev, "ref_pcs"), normalize)
+
+
 def _matrix(sample_pcs, ref_pcs, normalize, use_sqrt, use_EMD, dist):
     if use_EMD:
-        raise NotImplementedError("the earth mover's distance is not implemented (the reference has no EMD loss either)")
+        raise NotImplementedError("use_EMD is not wired to the earth mover's matrix: pass dist=emd_matrix(sample_pcs, "
+                                  "ref_pcs) for MMD-EMD / COV-EMD")
     if dist is None:
         dist = chamfer_matrix(sample_pcs, ref_pcs, normalize, use_sqrt)
     else:
@@ -76,7 +89,7 @@ def _matrix(sample_pcs, ref_pcs, normalize, use_sqrt, use_EMD, dist):
 def minimum_mathing_distance(sample_pcs, ref_pcs, batch_size=None, normalize=True, sess=None, verbose=False, use_sqrt=False,
                              use_EMD=False, dist=None):
     """-> (mmd: float, matched_dists: float32 numpy [R]): for every reference cloud the distance of the sample cloud
-    nearest to it, and their mean.  `dist`: a matrix from `chamfer_matrix` (the flags are then its own)."""
+    nearest to it, and their mean.  `dist`: a matrix from `chamfer_matrix` or `emd_matrix` (the flags are then its own)."""
     D = _matrix(sample_pcs, ref_pcs, normalize, use_sqrt, use_EMD, dist)
     _, _, col_min, _ = PC.match_min(D)
     matched_dists = col_min.cpu().numpy()
