@@ -686,8 +686,8 @@ int sivae_max_points_fwd(const float* x, float* vals, int* arg, int B, int C, in
 int sivae_max_points_bwd(const float* g, const int* arg, float* dx, int B, int C, int N, sivae_stream_t stream);
 /* The encoder's last stage in one piece: max over the points of BatchNorm1d(ReLU(a)), a [B][C][N], without y or the max's
  * dense gradient in memory.  _fwd: mean / invstd from sivae_relu_bn_stats (eval mode: the running mean and
- * rsqrt(running_var + eps)); y = relu(a) * (gamma invstd) + (beta - mean gamma invstd) is formed in registers with
- * sivae_relu_bn_apply's operations, so vals [B][C] and the int32 arg [B][C] are bit-identical to
+ * rsqrt(running_var + eps)); y = relu(a) * (gamma invstd) + (beta - mean gamma invstd) is formed in registers by the
+ * function sivae_relu_bn_apply's kernel stores, so vals [B][C] and the int32 arg [B][C] are bit-identical to
  * sivae_max_points_fwd(sivae_relu_bn_apply(a)): a NaN is the maximum, the lowest index wins among ties and among NaNs.
  * _bwd: from g [B][C] and the forward's arg.  dy is g at arg and zero elsewhere, so dbeta = sum_b g and
  * dgamma = invstd (sum_b g relu(a[b][c][arg]) - mean dbeta) are sums over B values per channel (fp64, fixed order; arg is

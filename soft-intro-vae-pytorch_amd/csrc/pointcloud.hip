@@ -275,7 +275,14 @@ __global__ void __launch_bounds__(64) relu_bn_finalize_kernel(const double* __re
   }
 }
 
-// dbeta = sum dy, dgamma = sum dy * rhat = invstd * (sum dy r - mean sum dy)
+// dbeta = sum dy, dgamma = sum dy * rhat = invstd * (sum dy r - mean sum dy), from channel c's two fp64 sums
+__device__ __forceinline__ void relu_bn_param_grads(int c, double sdy, double sdyr, const float* __restrict__ mean,
+                                                    const float* __restrict__ invstd, float* __restrict__ dgamma,
+                                                    float* __restrict__ dbeta) {
+  dbeta[c] = (float)sdy;
+  dgamma[c] = (float)((double)invstd[c] * (sdyr - (double)mean[c] * sdy));
+}
+
 __global__ void __launch_bounds__(64) relu_bn_bwd_finalize_kernel(const double* __restrict__ part, int S, int C,
                                                                   const float* __restrict__ mean,
                                                                   const float* __restrict__ invstd,
@@ -287,50 +294,97 @@ __global__ void __launch_bounds__(64) relu_bn_bwd_finalize_kernel(const double* 
     sdy += part[((size_t)c * S + s) * 2];
     sdyr += part[((size_t)c * S + s) * 2 + 1];
   }
-  dbeta[c] = (float)sdy;
-  dgamma[c] = (float)((double)invstd[c] * (sdyr - (double)mean[c] * sdy));
+  relu_bn_param_grads(c, sdy, sdyr, mean, invstd, dgamma, dbeta);
 }
 
-// BWD = false: y = gamma (relu(a) - mean) invstd + beta
-// BWD = true:  da = [a > 0] gamma invstd (dy - dbeta / m - rhat dgamma / m)
+// y = gamma (relu(a) - mean) invstd + beta as one FMA on relu(a), with sc = gamma invstd (one multiply) and
+// sh = beta - mean sc (one FMA).  These two functions are the only place the forward's arithmetic is written:
+// relu_bn_apply_kernel stores relu_bn_y, max_row<., true> walks over it, so the fused max sees the stored values bit for bit.
+__device__ __forceinline__ void relu_bn_scale_shift(int c, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    float& sc, float& sh) {
+  const float mu = mean[c], is = invstd[c], ga = gamma[c];
+  sc = ga * is;
+  sh = beta[c] - mu * sc;
+}
+__device__ __forceinline__ float relu_bn_y(float v, float sc, float sh) { return relu0(v) * sc + sh; }
+
 // One 16-byte access per tensor and thread (VEC; N % 4 == 0 keeps the four values in one row) — the store is the last
 // thing a thread does, so nothing recycles its data registers behind it (the store-data note in common.h).
-template <bool VEC, bool BWD>
-__global__ void __launch_bounds__(PC_NT) relu_bn_apply_kernel(const float* __restrict__ a, const float* __restrict__ dy,
-                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              const float* __restrict__ dgamma, const float* __restrict__ dbeta,
-                                                              float* __restrict__ out, int C, int N, size_t total,
-                                                              float inv_m) {
+template <bool VEC>
+__global__ void __launch_bounds__(PC_NT) relu_bn_apply_kernel(const float* __restrict__ a, const float* __restrict__ mean,
+                                                              const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float* __restrict__ y, int C,
+                                                              int N, size_t total) {
   const size_t e = ((size_t)blockIdx.x * PC_NT + threadIdx.x) * (VEC ? 4 : 1);
   if (e >= total) return;
-  const int c = (int)((e / (size_t)N) % (size_t)C);
-  const float mu = mean[c], is = invstd[c], ga = gamma[c];
-  if (!BWD) {
-    const float sc = ga * is, sh = beta[c] - mu * sc;
-    if (VEC) {
-      const float4 v = *reinterpret_cast<const float4*>(a + e);
-      *reinterpret_cast<float4*>(out + e) =
-          make_float4(relu0(v.x) * sc + sh, relu0(v.y) * sc + sh, relu0(v.z) * sc + sh, relu0(v.w) * sc + sh);
-    } else {
-      out[e] = relu0(a[e]) * sc + sh;
-    }
+  float sc, sh;
+  relu_bn_scale_shift((int)((e / (size_t)N) % (size_t)C), mean, invstd, gamma, beta, sc, sh);
+  if (VEC) {
+    const float4 v = *reinterpret_cast<const float4*>(a + e);
+    *reinterpret_cast<float4*>(y + e) =
+        make_float4(relu_bn_y(v.x, sc, sh), relu_bn_y(v.y, sc, sh), relu_bn_y(v.z, sc, sh), relu_bn_y(v.w, sc, sh));
   } else {
-    const float k = ga * is, mb = dbeta[c] * inv_m, mg = dgamma[c] * inv_m;
-#define PC_DA(A, G) ((A) > 0.f ? k * ((G) - mb - ((A) - mu) * is * mg) : 0.f)
-    if (VEC) {
-      const float4 v = *reinterpret_cast<const float4*>(a + e);
-      const float4 g = *reinterpret_cast<const float4*>(dy + e);
-      *reinterpret_cast<float4*>(out + e) = make_float4(PC_DA(v.x, g.x), PC_DA(v.y, g.y), PC_DA(v.z, g.z), PC_DA(v.w, g.w));
-    } else {
-      const float v = a[e];
-      out[e] = PC_DA(v, dy[e]);
-    }
-#undef PC_DA
+    y[e] = relu_bn_y(a[e], sc, sh);
   }
 }
 
-static inline bool pc_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// da = [a > 0] gamma invstd (dy - dbeta / m - rhat dgamma / m) with k = gamma invstd, mb = dbeta / m, mg = dgamma / m: the
+// only place the backward's arithmetic is written.  The gate is relu0's derivative (0 at a == 0 and at a NaN).
+__device__ __forceinline__ float relu_bn_da(float a, float dy, float k, float mb, float mu, float is, float mg) {
+  return a > 0.f ? k * (dy - mb - (a - mu) * is * mg) : 0.f;
+}
+
+// The backward's element-wise pass.  MAX = false: g is the dense dy [B][C][N] (sivae_relu_bn_bwd, arg unused).
+// MAX = true: dy is the max's gradient, g[row] at arg[row] and zero elsewhere, formed in registers (sivae_relu_bn_max_bwd:
+// one read of a, one write of da).  Accesses and the store as in relu_bn_apply_kernel.
+template <bool VEC, bool MAX>
+__global__ void __launch_bounds__(PC_NT) relu_bn_bwd_apply_kernel(const float* __restrict__ a, const float* __restrict__ g,
+                                                                  const int* __restrict__ arg, const float* __restrict__ mean,
+                                                                  const float* __restrict__ invstd,
+                                                                  const float* __restrict__ gamma,
+                                                                  const float* __restrict__ dgamma,
+                                                                  const float* __restrict__ dbeta, float* __restrict__ da,
+                                                                  int C, int N, size_t total, float inv_m) {
+  const size_t e = ((size_t)blockIdx.x * PC_NT + threadIdx.x) * (VEC ? 4 : 1);
+  if (e >= total) return;
+  const size_t row = e / (size_t)N;
+  const int c = (int)(row % (size_t)C), i = (int)(e - row * (size_t)N), kk = MAX ? arg[row] : 0;
+  const float gv = MAX ? g[row] : 0.f;
+  const float mu = mean[c], is = invstd[c], ga = gamma[c];
+  const float k = ga * is, mb = dbeta[c] * inv_m, mg = dgamma[c] * inv_m;
+  if (VEC) {
+    const float4 v = *reinterpret_cast<const float4*>(a + e);
+    const float4 d = !MAX ? *reinterpret_cast<const float4*>(g + e)
+                          : make_float4(i == kk ? gv : 0.f, i + 1 == kk ? gv : 0.f, i + 2 == kk ? gv : 0.f,
+                                        i + 3 == kk ? gv : 0.f);
+    *reinterpret_cast<float4*>(da + e) =
+        make_float4(relu_bn_da(v.x, d.x, k, mb, mu, is, mg), relu_bn_da(v.y, d.y, k, mb, mu, is, mg),
+                    relu_bn_da(v.z, d.z, k, mb, mu, is, mg), relu_bn_da(v.w, d.w, k, mb, mu, is, mg));
+  } else {
+    const float v = a[e];
+    da[e] = relu_bn_da(v, MAX ? (i == kk ? gv : 0.f) : g[e], k, mb, mu, is, mg);
+  }
+}
+
+// The 16-byte instantiations want N % 4 == 0 and every tensor they access that way on a 16-byte boundary.
+template <class... P>
+static inline bool pc_vec_ok(int N, const P*... ptrs) {
+  return (N & 3) == 0 && ((((uintptr_t)ptrs & 15) == 0) && ...);
+}
+
+// Launch of KV (16-byte accesses) on gridv where vec, of KS (scalar) on grids otherwise, in blocks of PC_NT threads on
+// `stream`; the argument list is written once.  PC_LAUNCH_ELEMS: an element-wise kernel, a thread owns four elements (KV)
+// or one (KS); PC_LAUNCH_ROWS: one wave per row.
+#define PC_LAUNCH(vec, KV, KS, gridv, grids, ...)                                  \
+  do {                                                                             \
+    if (vec) hipLaunchKernelGGL(KV, gridv, dim3(PC_NT), 0, stream, __VA_ARGS__);   \
+    else hipLaunchKernelGGL(KS, grids, dim3(PC_NT), 0, stream, __VA_ARGS__);       \
+  } while (0)
+#define PC_LAUNCH_ELEMS(vec, KV, KS, total, ...) \
+  PC_LAUNCH(vec, KV, KS, dim3(cdiv((total) / 4, PC_NT)), dim3(cdiv(total, PC_NT)), __VA_ARGS__)
+#define PC_LAUNCH_ROWS(vec, KV, KS, rows, ...) \
+  PC_LAUNCH(vec, KV, KS, dim3(cdiv(rows, PC_NT / 64)), dim3(cdiv(rows, PC_NT / 64)), __VA_ARGS__)
 
 static int relu_bn_check(int B, int C, int N) {
   if (B <= 0 || C <= 0 || N <= 0) return SIVAE_ERR_SHAPE;
@@ -354,12 +408,9 @@ extern "C" int sivae_relu_bn_stats(const float* a, int B, int C, int N, float ep
   const long long n = (long long)B * N;
   const RbPlan p = rb_plan(n, C);
   double* part = (double*)workspace;
-  if ((N & 3) == 0 && pc_aligned16(a))
-    hipLaunchKernelGGL((relu_bn_reduce_kernel<true, false>), dim3(C, p.S), dim3(PC_NT), 0, stream, a, (const float*)nullptr,
-                       part, C, N, n, p.len, p.S);
-  else
-    hipLaunchKernelGGL((relu_bn_reduce_kernel<false, false>), dim3(C, p.S), dim3(PC_NT), 0, stream, a, (const float*)nullptr,
-                       part, C, N, n, p.len, p.S);
+  const dim3 grid(C, p.S);
+  PC_LAUNCH(pc_vec_ok(N, a), (relu_bn_reduce_kernel<true, false>), (relu_bn_reduce_kernel<false, false>), grid, grid, a,
+            (const float*)nullptr, part, C, N, n, p.len, p.S);
   hipLaunchKernelGGL(relu_bn_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, stream, (const double*)part, p.S, C, (double)n,
                      eps, momentum, running_mean, running_var, num_batches_tracked, mean_out, invstd_out);
   return sivae_launch_status();
@@ -371,14 +422,8 @@ extern "C" int sivae_relu_bn_apply(const float* a, const float* mean, const floa
   const int rc = relu_bn_check(B, C, N);
   if (rc != SIVAE_OK) return rc;
   const size_t total = (size_t)B * C * N;
-  if ((N & 3) == 0 && pc_aligned16(a) && pc_aligned16(y))
-    hipLaunchKernelGGL((relu_bn_apply_kernel<true, false>), dim3(cdiv(total / 4, PC_NT)), dim3(PC_NT), 0, stream, a,
-                       (const float*)nullptr, mean, invstd, gamma, beta, (const float*)nullptr, (const float*)nullptr, y, C,
-                       N, total, 0.f);
-  else
-    hipLaunchKernelGGL((relu_bn_apply_kernel<false, false>), dim3(cdiv(total, PC_NT)), dim3(PC_NT), 0, stream, a,
-                       (const float*)nullptr, mean, invstd, gamma, beta, (const float*)nullptr, (const float*)nullptr, y, C,
-                       N, total, 0.f);
+  PC_LAUNCH_ELEMS(pc_vec_ok(N, a, y), (relu_bn_apply_kernel<true>), (relu_bn_apply_kernel<false>), total, a, mean, invstd,
+                  gamma, beta, y, C, N, total);
   return sivae_launch_status();
 }
 
@@ -393,23 +438,15 @@ extern "C" int sivae_relu_bn_bwd(const float* dy, const float* a, const float* m
   const RbPlan p = rb_plan(n, C);
   double* part = (double*)workspace;
   const size_t total = (size_t)B * C * N;
-  const bool vec = (N & 3) == 0 && pc_aligned16(a) && pc_aligned16(dy) && pc_aligned16(da);
-  if (vec)
-    hipLaunchKernelGGL((relu_bn_reduce_kernel<true, true>), dim3(C, p.S), dim3(PC_NT), 0, stream, a, dy, part, C, N, n, p.len,
-                       p.S);
-  else
-    hipLaunchKernelGGL((relu_bn_reduce_kernel<false, true>), dim3(C, p.S), dim3(PC_NT), 0, stream, a, dy, part, C, N, n,
-                       p.len, p.S);
+  const bool vec = pc_vec_ok(N, a, dy, da);
+  const dim3 grid(C, p.S);
+  PC_LAUNCH(vec, (relu_bn_reduce_kernel<true, true>), (relu_bn_reduce_kernel<false, true>), grid, grid, a, dy, part, C, N, n,
+            p.len, p.S);
   hipLaunchKernelGGL(relu_bn_bwd_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, stream, (const double*)part, p.S, C, mean,
                      invstd, dgamma, dbeta);
-  if (vec)
-    hipLaunchKernelGGL((relu_bn_apply_kernel<true, true>), dim3(cdiv(total / 4, PC_NT)), dim3(PC_NT), 0, stream, a, dy, mean,
-                       invstd, gamma, (const float*)nullptr, (const float*)dgamma, (const float*)dbeta, da, C, N, total,
-                       (float)(1.0 / (double)n));
-  else
-    hipLaunchKernelGGL((relu_bn_apply_kernel<false, true>), dim3(cdiv(total, PC_NT)), dim3(PC_NT), 0, stream, a, dy, mean,
-                       invstd, gamma, (const float*)nullptr, (const float*)dgamma, (const float*)dbeta, da, C, N, total,
-                       (float)(1.0 / (double)n));
+  PC_LAUNCH_ELEMS(vec, (relu_bn_bwd_apply_kernel<true, false>), (relu_bn_bwd_apply_kernel<false, false>), total, a, dy,
+                  (const int*)nullptr, mean, invstd, gamma, (const float*)dgamma, (const float*)dbeta, da, C, N, total,
+                  (float)(1.0 / (double)n));
   return sivae_launch_status();
 }
 
@@ -435,24 +472,23 @@ __device__ __forceinline__ void max_walk(float& bv, int& bi, float v, int i) {
   }
 }
 
-template <bool VEC>
-__global__ void __launch_bounds__(PC_NT) max_points_fwd_kernel(const float* __restrict__ x, float* __restrict__ vals,
-                                                               int* __restrict__ arg, int rows, int N) {
-  const int row = blockIdx.x * (PC_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;  // (wave-uniform)
-  const float* p = x + (size_t)row * N;
+// The walk over one row p[0 .. N) by one wave, the butterfly and the store.  BN: the value at i is relu_bn_y(p[i], sc, sh)
+// (the fused last encoder stage), else p[i] itself (sc, sh unused).
+template <bool VEC, bool BN>
+__device__ __forceinline__ void max_row(const float* p, int N, int lane, float sc, float sh, float* vals, int* arg, int row) {
+  const auto y = [=](float v) { return BN ? relu_bn_y(v, sc, sh) : v; };
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   if (VEC) {
     for (int i = lane * 4; i < N; i += 256) {
       const float4 v = *reinterpret_cast<const float4*>(p + i);
-      max_walk(bv, bi, v.x, i);
-      max_walk(bv, bi, v.y, i + 1);
-      max_walk(bv, bi, v.z, i + 2);
-      max_walk(bv, bi, v.w, i + 3);
+      max_walk(bv, bi, y(v.x), i);
+      max_walk(bv, bi, y(v.y), i + 1);
+      max_walk(bv, bi, y(v.z), i + 2);
+      max_walk(bv, bi, y(v.w), i + 3);
     }
   } else {
-    for (int i = lane; i < N; i += 64) max_walk(bv, bi, p[i], i);
+    for (int i = lane; i < N; i += 64) max_walk(bv, bi, y(p[i]), i);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -464,6 +500,14 @@ __global__ void __launch_bounds__(PC_NT) max_points_fwd_kernel(const float* __re
     vals[row] = bv;
     arg[row] = bi < N ? bi : 0;  // (a row of -inf only: no lane took an element; index 0)
   }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(PC_NT) max_points_fwd_kernel(const float* __restrict__ x, float* __restrict__ vals,
+                                                               int* __restrict__ arg, int rows, int N) {
+  const int row = blockIdx.x * (PC_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;  // (wave-uniform)
+  max_row<VEC, false>(x + (size_t)row * N, N, lane, 0.f, 0.f, vals, arg, row);
 }
 
 // dx = g[row] at arg[row], zero elsewhere: one kernel writes both
@@ -487,12 +531,7 @@ extern "C" int sivae_max_points_fwd(const float* x, float* vals, int* arg, int B
   const int rc = relu_bn_check(B, C, N);
   if (rc != SIVAE_OK) return rc;
   const int rows = B * C;
-  if ((N & 3) == 0 && pc_aligned16(x))
-    hipLaunchKernelGGL((max_points_fwd_kernel<true>), dim3(cdiv(rows, PC_NT / 64)), dim3(PC_NT), 0, stream, x, vals, arg, rows,
-                       N);
-  else
-    hipLaunchKernelGGL((max_points_fwd_kernel<false>), dim3(cdiv(rows, PC_NT / 64)), dim3(PC_NT), 0, stream, x, vals, arg,
-                       rows, N);
+  PC_LAUNCH_ROWS(pc_vec_ok(N, x), (max_points_fwd_kernel<true>), (max_points_fwd_kernel<false>), rows, x, vals, arg, rows, N);
   return sivae_launch_status();
 }
 
@@ -501,19 +540,15 @@ extern "C" int sivae_max_points_bwd(const float* g, const int* arg, float* dx, i
   const int rc = relu_bn_check(B, C, N);
   if (rc != SIVAE_OK) return rc;
   const size_t total = (size_t)B * C * N;
-  if ((N & 3) == 0 && pc_aligned16(dx))
-    hipLaunchKernelGGL((max_points_bwd_kernel<true>), dim3(cdiv(total / 4, PC_NT)), dim3(PC_NT), 0, stream, g, arg, dx, N,
-                       total);
-  else
-    hipLaunchKernelGGL((max_points_bwd_kernel<false>), dim3(cdiv(total, PC_NT)), dim3(PC_NT), 0, stream, g, arg, dx, N, total);
+  PC_LAUNCH_ELEMS(pc_vec_ok(N, dx), (max_points_bwd_kernel<true>), (max_points_bwd_kernel<false>), total, g, arg, dx, N, total);
   return sivae_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------ ReLU -> BatchNorm1d -> max
 // The encoder's last stage: y = BatchNorm1d(ReLU(a)) is only ever looked at through its max over the points, so neither y
-// nor the max's dense gradient has to exist.  Forward: max_points_fwd_kernel's walk with relu_bn_apply_kernel<., false>'s
-// expression formed in registers in front of it (the same operations on the same values: vals and arg are the
-// composition's, bit for bit); nothing of size B C N is written.  The statistics stay sivae_relu_bn_stats.
+// nor the max's dense gradient has to exist.  Forward: max_row over relu_bn_y, the function relu_bn_apply_kernel stores
+// (vals and arg are the composition's, bit for bit); nothing of size B C N is written.  The statistics stay
+// sivae_relu_bn_stats.
 template <bool VEC>
 __global__ void __launch_bounds__(PC_NT) relu_bn_max_fwd_kernel(const float* __restrict__ a, const float* __restrict__ mean,
                                                                 const float* __restrict__ invstd,
@@ -522,39 +557,14 @@ __global__ void __launch_bounds__(PC_NT) relu_bn_max_fwd_kernel(const float* __r
                                                                 int C, int N) {
   const int row = blockIdx.x * (PC_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;  // (wave-uniform)
-  const int c = row % C;
-  const float mu = mean[c], is = invstd[c], ga = gamma[c];
-  const float sc = ga * is, sh = beta[c] - mu * sc;
-  const float* p = a + (size_t)row * N;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  if (VEC) {
-    for (int i = lane * 4; i < N; i += 256) {
-      const float4 v = *reinterpret_cast<const float4*>(p + i);
-      max_walk(bv, bi, relu0(v.x) * sc + sh, i);
-      max_walk(bv, bi, relu0(v.y) * sc + sh, i + 1);
-      max_walk(bv, bi, relu0(v.z) * sc + sh, i + 2);
-      max_walk(bv, bi, relu0(v.w) * sc + sh, i + 3);
-    }
-  } else {
-    for (int i = lane; i < N; i += 64) max_walk(bv, bi, relu0(p[i]) * sc + sh, i);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    max_take(bv, bi, ov, oi);
-  }
-  if (lane == 0) {
-    vals[row] = bv;
-    arg[row] = bi < N ? bi : 0;  // (a row of -inf only: no lane took an element; index 0)
-  }
+  float sc, sh;
+  relu_bn_scale_shift(row % C, mean, invstd, gamma, beta, sc, sh);
+  max_row<VEC, true>(a + (size_t)row * N, N, lane, sc, sh, vals, arg, row);
 }
 
 // Backward, first launch.  The max's gradient dy is g[b][c] at arg[b][c] and zero elsewhere, so BatchNorm's two sums over
 // a channel's B N values are sums over B elements: sum dy = sum_b g, sum dy r = sum_b g relu(a[b][c][arg]).  One wave
 // per channel, lane l takes b = l, l + 64, ... in fp64, then the butterfly: a fixed order, two runs are bit-identical.
-// The formulas are relu_bn_bwd_finalize_kernel's.
 __global__ void __launch_bounds__(PC_NT) relu_bn_max_bwd_sums_kernel(const float* __restrict__ g, const int* __restrict__ arg,
                                                                      const float* __restrict__ a,
                                                                      const float* __restrict__ mean,
@@ -573,55 +583,18 @@ __global__ void __launch_bounds__(PC_NT) relu_bn_max_bwd_sums_kernel(const float
   }
   sdy = wave_sum(sdy);
   sdyr = wave_sum(sdyr);
-  if (lane == 0) {
-    dbeta[c] = (float)sdy;
-    dgamma[c] = (float)((double)invstd[c] * (sdyr - (double)mean[c] * sdy));
-  }
+  if (lane == 0) relu_bn_param_grads(c, sdy, sdyr, mean, invstd, dgamma, dbeta);
 }
 
-// Backward, second launch: relu_bn_apply_kernel<., true>'s expression with dy synthesised from (g, arg) — one read of a,
-// one write of da.  The store is the last thing a thread does (the store-data note in common.h).
-template <bool VEC>
-__global__ void __launch_bounds__(PC_NT) relu_bn_max_bwd_apply_kernel(const float* __restrict__ a, const float* __restrict__ g,
-                                                                      const int* __restrict__ arg,
-                                                                      const float* __restrict__ mean,
-                                                                      const float* __restrict__ invstd,
-                                                                      const float* __restrict__ gamma,
-                                                                      const float* __restrict__ dgamma,
-                                                                      const float* __restrict__ dbeta, float* __restrict__ da,
-                                                                      int C, int N, size_t total, float inv_m) {
-  const size_t e = ((size_t)blockIdx.x * PC_NT + threadIdx.x) * (VEC ? 4 : 1);
-  if (e >= total) return;
-  const size_t row = e / (size_t)N;
-  const int c = (int)(row % (size_t)C), i = (int)(e - row * (size_t)N), kk = arg[row];
-  const float gv = g[row];
-  const float mu = mean[c], is = invstd[c], ga = gamma[c];
-  const float k = ga * is, mb = dbeta[c] * inv_m, mg = dgamma[c] * inv_m;
-#define PC_DA(A, G) ((A) > 0.f ? k * ((G) - mb - ((A) - mu) * is * mg) : 0.f)
-  if (VEC) {
-    const float4 v = *reinterpret_cast<const float4*>(a + e);
-    *reinterpret_cast<float4*>(da + e) =
-        make_float4(PC_DA(v.x, i == kk ? gv : 0.f), PC_DA(v.y, i + 1 == kk ? gv : 0.f), PC_DA(v.z, i + 2 == kk ? gv : 0.f),
-                    PC_DA(v.w, i + 3 == kk ? gv : 0.f));
-  } else {
-    const float v = a[e];
-    da[e] = PC_DA(v, i == kk ? gv : 0.f);
-  }
-#undef PC_DA
-}
-
+// Backward, second launch: relu_bn_bwd_apply_kernel<., true>.
 extern "C" int sivae_relu_bn_max_fwd(const float* a, const float* mean, const float* invstd, const float* gamma,
                                      const float* beta, float* vals, int* arg, int B, int C, int N, hipStream_t stream) {
   if (!a || !mean || !invstd || !gamma || !beta || !vals || !arg) return SIVAE_ERR_NULL;
   const int rc = relu_bn_check(B, C, N);
   if (rc != SIVAE_OK) return rc;
   const int rows = B * C;
-  if ((N & 3) == 0 && pc_aligned16(a))
-    hipLaunchKernelGGL((relu_bn_max_fwd_kernel<true>), dim3(cdiv(rows, PC_NT / 64)), dim3(PC_NT), 0, stream, a, mean, invstd,
-                       gamma, beta, vals, arg, rows, C, N);
-  else
-    hipLaunchKernelGGL((relu_bn_max_fwd_kernel<false>), dim3(cdiv(rows, PC_NT / 64)), dim3(PC_NT), 0, stream, a, mean, invstd,
-                       gamma, beta, vals, arg, rows, C, N);
+  PC_LAUNCH_ROWS(pc_vec_ok(N, a), (relu_bn_max_fwd_kernel<true>), (relu_bn_max_fwd_kernel<false>), rows, a, mean, invstd, gamma,
+                 beta, vals, arg, rows, C, N);
   return sivae_launch_status();
 }
 
@@ -635,11 +608,7 @@ extern "C" int sivae_relu_bn_max_bwd(const float* g, const int* arg, const float
   const float inv_m = (float)(1.0 / (double)((long long)B * N));
   hipLaunchKernelGGL(relu_bn_max_bwd_sums_kernel, dim3(cdiv(C, PC_NT / 64)), dim3(PC_NT), 0, stream, g, arg, a, mean, invstd,
                      dgamma, dbeta, B, C, N);
-  if ((N & 3) == 0 && pc_aligned16(a) && pc_aligned16(da))
-    hipLaunchKernelGGL((relu_bn_max_bwd_apply_kernel<true>), dim3(cdiv(total / 4, PC_NT)), dim3(PC_NT), 0, stream, a, g, arg,
-                       mean, invstd, gamma, (const float*)dgamma, (const float*)dbeta, da, C, N, total, inv_m);
-  else
-    hipLaunchKernelGGL((relu_bn_max_bwd_apply_kernel<false>), dim3(cdiv(total, PC_NT)), dim3(PC_NT), 0, stream, a, g, arg, mean,
-                       invstd, gamma, (const float*)dgamma, (const float*)dbeta, da, C, N, total, inv_m);
+  PC_LAUNCH_ELEMS(pc_vec_ok(N, a, da), (relu_bn_bwd_apply_kernel<true, true>), (relu_bn_bwd_apply_kernel<false, true>), total,
+                  a, g, arg, mean, invstd, gamma, (const float*)dgamma, (const float*)dbeta, da, C, N, total, inv_m);
   return sivae_launch_status();
 }

@@ -250,6 +250,22 @@ def _require_clouds(pcs, who):
     return pcs.shape[0], pcs.shape[1], pcs.stride()
 
 
+def _both_require_clouds(sample, ref, who, max_points=None):
+    """the checks of a set-to-set matrix, sample [S, M, 3] against ref [R, N, 3] -> (S, M, sample strides, R, N, ref strides)"""
+    for pcs in (sample, ref):  # (the shape error before the device's, as relu_bn_max does)
+        if pcs.dim() != 3 or pcs.shape[2] != 3:
+            raise ValueError("sivae_hip.%s: expected point clouds [S, N, 3], got %s" % (who, tuple(pcs.shape)))
+    S, M, sa = _require_clouds(sample, who)
+    R, N, sb = _require_clouds(ref, who)
+    if sample.device != ref.device:
+        raise ValueError("sivae_hip.%s: sample is on %s, ref on %s" % (who, sample.device, ref.device))
+    if max_points is not None and (M > max_points or N > max_points):
+        raise ValueError("sivae_hip.%s: clouds of %d and %d points, at most %d are supported" % (who, M, N, max_points))
+    if S * R >= 0x7fffffff:
+        raise ValueError("sivae_hip.%s: %d x %d cloud pairs do not fit an int32 index" % (who, S, R))
+    return S, M, sa, R, N, sb
+
+
 def occupancy_grid(pcs, resolution, in_sphere=False, want_bernoulli=True, return_status=False):
     """_entropy_of_occupancy_grid's counting (metrics/jsd.py:113-126): -> (counters, bernoulli), int32 [G] each, over the
     resolution^3 cells (the ones inside the sphere when in_sphere); bernoulli is None when not wanted.  return_status:
@@ -328,15 +344,7 @@ def chamfer_matrix(sample, ref, normalize=True, use_sqrt=False):
     `transpose(1, 2)` view of a [S, 3, M] decoder output is read in place) -> D [S, R] float32 with
     D[s, r] = sum_j f(min_i |P_j - Q_i|^2) / m + sum_i f(min_j |P_j - Q_i|^2) / n, f = sqrt when use_sqrt, m = M and n = N
     when normalize (1 otherwise).  A cloud with a non-finite coordinate makes its row / column of D non-finite."""
-    for pcs in (sample, ref):  # (the shape error before the device's, as relu_bn_max does)
-        if pcs.dim() != 3 or pcs.shape[2] != 3:
-            raise ValueError("sivae_hip.chamfer_matrix: expected point clouds [S, N, 3], got %s" % (tuple(pcs.shape),))
-    S, M, sa = _require_clouds(sample, "chamfer_matrix")
-    R, N, sb = _require_clouds(ref, "chamfer_matrix")
-    if sample.device != ref.device:
-        raise ValueError("sivae_hip.chamfer_matrix: sample is on %s, ref on %s" % (sample.device, ref.device))
-    if S * R >= 0x7fffffff:
-        raise ValueError("sivae_hip.chamfer_matrix: %d x %d cloud pairs do not fit an int32 index" % (S, R))
+    S, M, sa, R, N, sb = _both_require_clouds(sample, ref, "chamfer_matrix")
     D = torch.empty((S, R), dtype=torch.float32, device=sample.device)
     slab = max(1, min(S, MATRIX_POINT_PAIRS_PER_LAUNCH // (R * M * N)))
     ws = workspace(_lib.load().sivae_chamfer_matrix_workspace_bytes(slab, R, M, N), sample.device)
@@ -387,17 +395,7 @@ def emd_matrix(sample, ref, normalize=True):
     -> D [S, R] float32 with D[s, r] = EMD(left = ref_r, right = sample_s): the cost of the matching, divided by
     max(M, N) when normalize.  Not symmetric in its arguments.  A cloud with a non-finite coordinate makes its row /
     column of D NaN."""
-    for pcs in (sample, ref):  # (the shape error before the device's, as chamfer_matrix does)
-        if pcs.dim() != 3 or pcs.shape[2] != 3:
-            raise ValueError("sivae_hip.emd_matrix: expected point clouds [S, N, 3], got %s" % (tuple(pcs.shape),))
-    S, M, sa = _require_clouds(sample, "emd_matrix")
-    R, N, sb = _require_clouds(ref, "emd_matrix")
-    if sample.device != ref.device:
-        raise ValueError("sivae_hip.emd_matrix: sample is on %s, ref on %s" % (sample.device, ref.device))
-    if M > EMD_MAX_POINTS or N > EMD_MAX_POINTS:
-        raise ValueError("sivae_hip.emd_matrix: clouds of %d and %d points, at most %d are supported" % (M, N, EMD_MAX_POINTS))
-    if S * R >= 0x7fffffff:
-        raise ValueError("sivae_hip.emd_matrix: %d x %d cloud pairs do not fit an int32 index" % (S, R))
+    S, M, sa, R, N, sb = _both_require_clouds(sample, ref, "emd_matrix", max_points=EMD_MAX_POINTS)
     D = torch.empty((S, R), dtype=torch.float32, device=sample.device)
     pairs = max(1, EMD_POINT_PAIRS_PER_LAUNCH // (M * N))    # cloud pairs one launch may cover:
     rows, cols = max(1, min(S, pairs // R)), min(R, pairs)   # a slab of whole rows, or ONE row in blocks of columns
@@ -444,15 +442,19 @@ def chamfer_distance(preds, gts, return_indices=False):
     return (loss, idx_p, idx_g) if return_indices else loss
 
 
+def _bn_mean_invstd(a, st):
+    """-> (mean, invstd): the batch's in training (the running buffers get their update), else the running buffers'"""
+    if st.training:
+        return relu_bn_stats(a, st.running_mean, st.running_var, st.num_batches_tracked, st.eps,
+                             st.momentum if st.momentum is not None else 0.1)
+    return st.running_mean, torch.rsqrt(st.running_var + st.eps)
+
+
 class ReluBnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, weight, bias, st):
         a = a.contiguous()
-        if st.training:
-            mean, invstd = relu_bn_stats(a, st.running_mean, st.running_var, st.num_batches_tracked, st.eps,
-                                         st.momentum if st.momentum is not None else 0.1)
-        else:
-            mean, invstd = st.running_mean, torch.rsqrt(st.running_var + st.eps)
+        mean, invstd = _bn_mean_invstd(a, st)
         ctx.training = st.training
         ctx.save_for_backward(a, mean, invstd, weight)
         return relu_bn_apply(a, mean, invstd, weight.detach(), bias.detach())
@@ -494,11 +496,7 @@ class ReluBnMaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, weight, bias, st):
         a = a.contiguous()
-        if st.training:
-            mean, invstd = relu_bn_stats(a, st.running_mean, st.running_var, st.num_batches_tracked, st.eps,
-                                         st.momentum if st.momentum is not None else 0.1)
-        else:
-            mean, invstd = st.running_mean, torch.rsqrt(st.running_var + st.eps)
+        mean, invstd = _bn_mean_invstd(a, st)
         vals, arg = relu_bn_max_fwd(a, mean, invstd, weight.detach(), bias.detach())
         ctx.training = st.training
         ctx.save_for_backward(a, mean, invstd, weight, arg)

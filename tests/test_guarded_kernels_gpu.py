@@ -22,6 +22,7 @@ import kernel_checks16 as kc16
 import pc3d_jsd_oracle as JO
 import pc3d_oracle as O
 from support.guard import describe, guarded
+from support.pc import viol
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -384,15 +385,6 @@ def test_slab_view_destination(name):
 
 
 # ------------------------------------------------------------------------------------------------ c. point clouds
-def _viol(a, b, rtol=1e-4, atol_scale=1e-5):
-    """the project's element-wise criterion (tests/test_pointcloud_gpu.py): <= 1 passes"""
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    if not torch.isfinite(a).all():
-        return float("inf")
-    atol = atol_scale * float(b.abs().max())
-    return float(((a - b).abs() / (rtol * b.abs() + atol + 1e-300)).max())
-
-
 PC_B, PC_M, PC_C = 3, 70, 5
 PC_N = [131, 132]  # N & 3 != 0: the scalar kernels; N & 3 == 0 on 16-byte-aligned tensors: the vector ones
 
@@ -460,8 +452,8 @@ def test_guarded_relu_bn_and_max_points(N):
         vals, arg = PC.max_points_fwd(x.to(DEV))
         dx = PC.max_points_bwd(gy.to(DEV), arg, N)
         _intact(g)
-    figs = dict(y=_viol(y, y64), rm=_viol(rm, rm64), rv=_viol(rv, rv64), da=_viol(da, a64.grad),
-                dgamma=_viol(dgamma, g64.grad), dbeta=_viol(dbeta, b64.grad))
+    figs = dict(y=viol(y, y64), rm=viol(rm, rm64), rv=viol(rv, rv64), da=viol(da, a64.grad),
+                dgamma=viol(dgamma, g64.grad), dbeta=viol(dbeta, b64.grad))
     assert all(v <= 1.0 for v in figs.values()), figs
     assert int(nbt) == 4 and bool((da[ad == 0] == 0).all()) and bool((da[:, 0] == 0).all())
     want = x.max(dim=2)[0]
@@ -489,7 +481,7 @@ def test_guarded_pointwise_conv(N):
         y = PC.pointwise_conv(ld[0], ld[1], ld[2], relu=True)
         (y * dy.to(DEV)).sum().backward()
         _intact(g)
-    assert _viol(y, y64) <= 1.0 and _viol(ld[0].grad, l64[0].grad) <= 1.0
+    assert viol(y, y64) <= 1.0 and viol(ld[0].grad, l64[0].grad) <= 1.0
     for got, ref, r32 in zip(ld[1:], l64[1:], runs[torch.float32][1][1:]):  # (test_pointcloud_gpu._grad_report's gate)
         assert bool(torch.isfinite(got.grad).all())
         assert O.rel_l2(got.grad, ref.grad) <= max(4 * O.rel_l2(r32.grad, ref.grad), 1e-5)

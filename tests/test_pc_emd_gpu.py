@@ -23,18 +23,13 @@ import torch
 
 import pc3d_emd_oracle as MO
 import pc3d_eval_oracle as EO
+from support.pc import DEV, _PC, put
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 # (M, N, S, R, normalize)
 VALUE_CASES = [(1, 1, 2, 3, True), (1, 9, 2, 3, True), (5, 7, 2, 3, True), (64, 64, 2, 3, True), (255, 257, 2, 3, True),
                (257, 300, 2, 3, True), (1025, 2049, 1, 1, True), (2049, 1025, 1, 1, True), (4096, 3, 2, 3, True),
                (3, 3073, 1, 1, True), (5, 7, 2, 3, False), (257, 300, 2, 3, False)]
-
-
-def _PC():
-    from sivae_hip import pointcloud as PC
-    return PC
 
 
 def _E():
@@ -73,10 +68,6 @@ def _gate():
     return 16 * worst
 
 
-def _dev(a):
-    return torch.from_numpy(np.array(a)).to(DEV)
-
-
 def _host(D):
     D = D.double().cpu().numpy()
     assert np.isfinite(D).all()
@@ -87,7 +78,7 @@ def _host(D):
 def test_values_against_the_float64_oracle(M, N, S, R, normalize):
     PC = _PC()
     sample, ref = _clouds(S, R, M, N)
-    D = PC.emd_matrix(_dev(sample), _dev(ref), normalize=normalize)
+    D = PC.emd_matrix(put(sample), put(ref), normalize=normalize)
     assert D.shape == (S, R) and D.dtype == torch.float32 and D.is_contiguous()
     w = _rel(_host(D), _ref(S, R, M, N, normalize))
     print("emd_matrix M=%d N=%d S=%d R=%d normalize=%s: worst relative error %.3e (gate %.3e)"
@@ -139,7 +130,7 @@ def test_a_cloud_against_itself(n, side, how):
     gap = _closest_pair(x[0])
     assert gap >= RESOLVED_GAP, "closest pair %.4f: the first level does not resolve this cloud" % gap
     y = x[:, np.random.default_rng(n).permutation(n)] if how == "permuted" else x
-    D = float(PC.emd_matrix(_dev(x), _dev(y), normalize=True)[0, 0])
+    D = float(PC.emd_matrix(put(x), put(y), normalize=True)[0, 0])
     diam = _diameter(x[0])
     print("emd_matrix of a %d-point cloud (cube of side %g) against %s: %.3e (closest pair %.3f, diameter %.3f, bound %.3e)"
           % (n, side, "itself" if how == "identical" else "a permutation of itself", D, gap, diam, 1e-5 * diam))
@@ -166,7 +157,7 @@ def test_a_dense_cloud_against_itself_matches_the_oracle(n, how):
     gate = 16 * abs(D32 - D64) / D64
     assert 0 < gate < 1e-4, gate
     y = x[:, np.random.default_rng(n).permutation(n)] if how == "permuted" else x
-    D = float(PC.emd_matrix(_dev(x), _dev(y))[0, 0])
+    D = float(PC.emd_matrix(put(x), put(y))[0, 0])
     print("%d-point unit-cube cloud against %s: %.6e, float64 oracle %.6e, relative error %.3e (float32 oracle %.3e, gate "
           "%.3e)" % (n, "itself" if how == "identical" else "a permutation of itself", D, D64, abs(D - D64) / D64,
                      abs(D32 - D64) / D64, gate))
@@ -180,9 +171,9 @@ def test_full_size_clouds():
     PC = _PC()
     sample, ref = _clouds(1, 2, 4096, 4096)
     rng = np.random.default_rng(4096)
-    D = PC.emd_matrix(_dev(sample), _dev(ref))
-    assert torch.equal(D, PC.emd_matrix(_dev(sample), _dev(ref)))
-    Dp = PC.emd_matrix(_dev(sample[:, rng.permutation(4096)]), _dev(ref[:, rng.permutation(4096)]))
+    D = PC.emd_matrix(put(sample), put(ref))
+    assert torch.equal(D, PC.emd_matrix(put(sample), put(ref)))
+    Dp = PC.emd_matrix(put(sample[:, rng.permutation(4096)]), put(ref[:, rng.permutation(4096)]))
     D, Dp = _host(D), _host(Dp)
     assert (D > 0.01).all() and (D < 1.0).all()      # (unrelated uniform clouds: a fraction of the cube's side)
     print("4096-point clouds %s, their points permuted %s" % (D.tolist(), Dp.tolist()))
@@ -193,14 +184,14 @@ def test_full_size_clouds():
 @pytest.mark.parametrize("S,R,M,N", [(3, 5, 33, 70), (1, 2, 2049, 1025), (50, 50, 16, 16)])
 def test_two_runs_are_bit_identical(S, R, M, N):
     PC = _PC()
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     for normalize in (True, False):
         assert torch.equal(PC.emd_matrix(sample, ref, normalize), PC.emd_matrix(sample, ref, normalize))
 
 
 def _transposed_view(a):
     """the [S, N, 3] view of [S, 3, N] storage: what evaluation/generate_data_for_metrics.py's transpose_(1, 2) yields"""
-    v = _dev(a).permute(0, 2, 1).contiguous().transpose(1, 2)
+    v = put(a).permute(0, 2, 1).contiguous().transpose(1, 2)
     assert not v.is_contiguous() and v.stride(2) == a.shape[1]
     return v
 
@@ -209,9 +200,9 @@ def _transposed_view(a):
 def test_layouts_change_no_bit(S, R, M, N):
     PC = _PC()
     sample, ref = _clouds(S, R, M, N)
-    base = PC.emd_matrix(_dev(sample), _dev(ref))
-    for name, s, r in (("sample transposed", _transposed_view(sample), _dev(ref)),
-                       ("ref transposed", _dev(sample), _transposed_view(ref)),
+    base = PC.emd_matrix(put(sample), put(ref))
+    for name, s, r in (("sample transposed", _transposed_view(sample), put(ref)),
+                       ("ref transposed", put(sample), _transposed_view(ref)),
                        ("both transposed", _transposed_view(sample), _transposed_view(ref))):
         assert torch.equal(PC.emd_matrix(s, r), base), name
 
@@ -228,7 +219,7 @@ def test_slabs_change_no_bit(monkeypatch, normalize):
     """(3, 5, 33, 70) in one launch and in three launches of one row each"""
     PC = _PC()
     S, R, M, N = 3, 5, 33, 70
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     calls = _count_launches(monkeypatch, PC)
     whole = PC.emd_matrix(sample, ref, normalize=normalize)
     assert calls.count("sivae_emd_matrix") == 1
@@ -243,7 +234,7 @@ def test_a_true_row_slab_of_the_entry_point():
     rows s0 .. s1 - 1 bit for bit, every other element of D untouched"""
     PC = _PC()
     S, R, M, N = 5, 4, 33, 70
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     whole = PC.emd_matrix(sample, ref)
     D = torch.full((S, R), -7.0, dtype=torch.float32, device=DEV)
     ws = PC.workspace(PC._lib.load().sivae_emd_matrix_workspace_bytes(2, R, M, N), sample.device)
@@ -258,7 +249,7 @@ def test_long_rows_go_in_column_blocks(monkeypatch):
     """(3, 5, 33, 70) with two cloud pairs to a launch: every row in blocks of 2, 2 and 1 columns"""
     PC = _PC()
     S, R, M, N = 3, 5, 33, 70
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     whole = PC.emd_matrix(sample, ref)
     calls = _count_launches(monkeypatch, PC)
     monkeypatch.setattr(PC, "EMD_POINT_PAIRS_PER_LAUNCH", 2 * M * N)
@@ -275,7 +266,7 @@ def test_more_pairs_than_blocks_against_row_slabs(monkeypatch):
     decides the split differently, and the float32 ORACLE is off by 6.8e-5 on its worst entry of this matrix."""
     PC = _PC()
     S, R, M, N = 50, 50, 16, 16
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     calls = _count_launches(monkeypatch, PC)
     whole = PC.emd_matrix(sample, ref)
     assert calls.count("sivae_emd_matrix") == 1
@@ -310,8 +301,8 @@ def test_order_convention():
     other = np.array([[MO.emd(sample[s], ref[r]) for r in range(3)] for s in range(2)])
     apart = float((np.abs(want - other) / want).min())
     assert apart >= 100 * _gate(), apart
-    D = _host(PC.emd_matrix(_dev(sample), _dev(ref)))
-    Dsw = _host(PC.emd_matrix(_dev(ref), _dev(sample))).T
+    D = _host(PC.emd_matrix(put(sample), put(ref)))
+    Dsw = _host(PC.emd_matrix(put(ref), put(sample))).T
     print("order convention: oracle's two orders differ by %.3e at least; kernel against the oracle %.3e, swapped call "
           "against the other order %.3e" % (apart, _rel(D, want), _rel(Dsw, other)))
     assert _rel(D, want) <= _gate() and _rel(Dsw, other) <= _gate()
@@ -323,11 +314,11 @@ def test_non_finite_coordinates_stay_in_their_row_and_column(normalize):
     PC = _PC()
     S, R, M, N = 3, 5, 33, 70
     sample, ref = (np.array(a) for a in _clouds(S, R, M, N))
-    clean = PC.emd_matrix(_dev(sample), _dev(ref), normalize)
+    clean = PC.emd_matrix(put(sample), put(ref), normalize)
     assert bool(torch.isfinite(clean).all())
     sample[1, 17, 2] = np.nan
     ref[3, 69, 0] = np.inf
-    D = PC.emd_matrix(_dev(sample), _dev(ref), normalize)
+    D = PC.emd_matrix(put(sample), put(ref), normalize)
     bad = torch.zeros(S, R, dtype=torch.bool, device=DEV)
     bad[1, :] = True
     bad[:, 3] = True
@@ -348,13 +339,13 @@ def test_drop_in_mmd_and_cov():
     D64 = _ref(S, R, M, N, True, seed)
     gap = EO.smallest_gap(D64)
     assert gap >= 100 * _gate(), "argmin gap %.2e: float32 cannot be asked for the float64 argmin" % gap
-    D = PC.emd_matrix(_dev(sample), _dev(ref))
+    D = PC.emd_matrix(put(sample), put(ref))
     assert _rel(_host(D), D64) <= _gate()
     De = E.emd_matrix(np.array(sample), np.array(ref))
     assert De.is_cuda and torch.equal(De, D)
-    assert torch.equal(E.emd_matrix(torch.from_numpy(np.array(sample)), _dev(ref)), D)
+    assert torch.equal(E.emd_matrix(torch.from_numpy(np.array(sample)), put(ref)), D)
     assert torch.equal(E.emd_matrix(np.array(sample), np.array(ref), normalize=False),
-                       PC.emd_matrix(_dev(sample), _dev(ref), normalize=False))
+                       PC.emd_matrix(put(sample), put(ref), normalize=False))
     mmd64, matched64, _ = EO.minimum_matching_distance(D64)
     cov64, ref64, dist64 = EO.coverage(D64)
     for x_g, x, dist in ((np.array(sample), np.array(ref), D), (None, None, D.cpu().numpy())):
@@ -365,7 +356,7 @@ def test_drop_in_mmd_and_cov():
         assert np.all(np.abs(matched_dist - dist64) <= _gate() * dist64)
         assert np.array_equal(matched_ref, ref64) and cov == cov64
     with pytest.raises(NotImplementedError):
-        E.coverage(_dev(sample), _dev(ref), use_EMD=True)
+        E.coverage(put(sample), put(ref), use_EMD=True)
 
 
 # ------------------------------------------------------------------------------------------------ guarded
@@ -375,7 +366,7 @@ def test_guarded(S, R, M, N):
     written outside a tensor, no element left at the poison value, the unguarded results"""
     from sivae_hip import ops, pointcloud
     from support.guard import describe, guarded
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     D0 = pointcloud.emd_matrix(sample, ref)
     with guarded(pointcloud) as g:  # (pointcloud's names only: its torch; `workspace` is ops' and needs ops in the list)
         D1 = pointcloud.emd_matrix(sample, ref)

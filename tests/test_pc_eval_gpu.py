@@ -22,9 +22,9 @@ import pytest
 import torch
 
 import pc3d_eval_oracle as EO
+from support.pc import DEV, _PC, put
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 TOL = 1e-5
 CASES = [(3, 5, 33, 70), (1, 1, 1, 1), (2, 3, 2053, 300), (3, 2, 300, 2053), (1, 2, 2053, 1030), (70, 130, 8, 8),
          (300, 300, 4, 4), (2, 2, 700, 64), (2, 2, 1300, 64)]
@@ -32,11 +32,6 @@ FLAGS = [(True, False), (True, True), (False, False), (False, True)]  # (normali
 # (seed, S, R, M, N) of the metric checks: the generator asserts the argmin gap of each
 METRIC_CASES = [(2024, 6, 9, 40, 55), (2025, 9, 6, 55, 40), (2026, 12, 5, 33, 70)]
 MIN_GAP = 1e-4
-
-
-def _PC():
-    from sivae_hip import pointcloud as PC
-    return PC
 
 
 def _E():
@@ -62,10 +57,6 @@ def _ref(S, R, M, N, normalize, use_sqrt, seed=None):
     return D
 
 
-def _dev(a):
-    return torch.from_numpy(np.array(a)).to(DEV)
-
-
 def _worst(D, D64):
     """largest |D - D64| / |D64| (0 / 0 counts as 0: an exact zero must be met exactly)"""
     D = D.double().cpu().numpy()
@@ -81,7 +72,7 @@ def _worst(D, D64):
 def test_matrix_parity(S, R, M, N, normalize, use_sqrt):
     PC = _PC()
     sample, ref = _clouds(S, R, M, N)
-    D = PC.chamfer_matrix(_dev(sample), _dev(ref), normalize=normalize, use_sqrt=use_sqrt)
+    D = PC.chamfer_matrix(put(sample), put(ref), normalize=normalize, use_sqrt=use_sqrt)
     assert D.shape == (S, R) and D.dtype == torch.float32 and D.is_contiguous()
     w = _worst(D, _ref(S, R, M, N, normalize, use_sqrt))
     print("chamfer_matrix (%d, %d, %d, %d) normalize=%s use_sqrt=%s: worst relative error %.3e"
@@ -94,7 +85,7 @@ def test_slabs_change_no_bit(monkeypatch, normalize, use_sqrt):
     """(3, 5, 33, 70) in three launches of one row each"""
     PC = _PC()
     S, R, M, N = 3, 5, 33, 70
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     whole = PC.chamfer_matrix(sample, ref, normalize=normalize, use_sqrt=use_sqrt)
     calls = []
     real = PC._lib.call
@@ -107,7 +98,7 @@ def test_slabs_change_no_bit(monkeypatch, normalize, use_sqrt):
 
 def test_same_set_on_both_sides_has_an_exact_zero_diagonal():
     PC = _PC()
-    x = _dev(_clouds(4, 4, 256, 256)[0])
+    x = put(_clouds(4, 4, 256, 256)[0])
     for normalize, use_sqrt in FLAGS:
         D = PC.chamfer_matrix(x, x, normalize=normalize, use_sqrt=use_sqrt)
         assert torch.equal(D.diagonal(), torch.zeros(4, device=DEV))
@@ -120,7 +111,7 @@ def test_same_set_on_both_sides_has_an_exact_zero_diagonal():
 def test_diagonal_agrees_with_the_training_kernel(B, M, N):
     """D[b, b] without normalisation is chamfer_fwd's loss[b]: other summation order, so 1e-5 and no bit equality"""
     PC = _PC()
-    sample, ref = (_dev(a) for a in _clouds(B, B, M, N))
+    sample, ref = (put(a) for a in _clouds(B, B, M, N))
     D = PC.chamfer_matrix(sample, ref, normalize=False)
     loss = PC.chamfer_fwd(sample, ref)[0]
     rel = ((D.diagonal().double() - loss.double()).abs() / loss.double()).max()
@@ -130,18 +121,8 @@ def test_diagonal_agrees_with_the_training_kernel(B, M, N):
 
 def _transposed_view(a):
     """the [S, N, 3] view of [S, 3, N] storage: what evaluation/generate_data_for_metrics.py's transpose_(1, 2) yields"""
-    v = _dev(a).permute(0, 2, 1).contiguous().transpose(1, 2)
+    v = put(a).permute(0, 2, 1).contiguous().transpose(1, 2)
     assert not v.is_contiguous() and v.stride(2) == a.shape[1]
-    return v
-
-
-def _misaligned(a):
-    """a contiguous copy whose base address lies one float behind a 16-byte boundary"""
-    t = torch.from_numpy(np.array(a))
-    buf = torch.empty(t.numel() + 8, dtype=torch.float32, device=DEV)
-    v = buf[1:1 + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4
     return v
 
 
@@ -149,19 +130,19 @@ def _misaligned(a):
 def test_layouts_change_no_bit(S, R, M, N):
     PC = _PC()
     sample, ref = _clouds(S, R, M, N)
-    base = PC.chamfer_matrix(_dev(sample), _dev(ref))
-    for name, s, r in (("sample transposed", _transposed_view(sample), _dev(ref)),
-                       ("ref transposed", _dev(sample), _transposed_view(ref)),
+    base = PC.chamfer_matrix(put(sample), put(ref))
+    for name, s, r in (("sample transposed", _transposed_view(sample), put(ref)),
+                       ("ref transposed", put(sample), _transposed_view(ref)),
                        ("both transposed", _transposed_view(sample), _transposed_view(ref)),
-                       ("sample misaligned", _misaligned(sample), _dev(ref)),
-                       ("ref misaligned", _dev(sample), _misaligned(ref))):
+                       ("sample misaligned", put(sample, misaligned=True), put(ref)),
+                       ("ref misaligned", put(sample), put(ref, misaligned=True))):
         assert torch.equal(PC.chamfer_matrix(s, r), base), name
 
 
 @pytest.mark.parametrize("S,R,M,N", [(3, 5, 33, 70), (1, 2, 2053, 1030), (70, 130, 8, 8)])
 def test_two_runs_are_bit_identical(S, R, M, N):
     PC = _PC()
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     for normalize, use_sqrt in FLAGS:
         assert torch.equal(PC.chamfer_matrix(sample, ref, normalize, use_sqrt),
                            PC.chamfer_matrix(sample, ref, normalize, use_sqrt))
@@ -172,10 +153,10 @@ def test_non_finite_coordinates_stay_in_their_row_and_column(normalize, use_sqrt
     PC, E = _PC(), _E()
     S, R, M, N = 3, 5, 33, 70
     sample, ref = (np.array(a) for a in _clouds(S, R, M, N))
-    clean = PC.chamfer_matrix(_dev(sample), _dev(ref), normalize, use_sqrt)
+    clean = PC.chamfer_matrix(put(sample), put(ref), normalize, use_sqrt)
     sample[1, 17, 2] = np.nan
     ref[3, 69, 0] = np.inf
-    D = PC.chamfer_matrix(_dev(sample), _dev(ref), normalize, use_sqrt)
+    D = PC.chamfer_matrix(put(sample), put(ref), normalize, use_sqrt)
     bad = torch.zeros(S, R, dtype=torch.bool, device=DEV)
     bad[1, :] = True
     bad[:, 3] = True
@@ -214,10 +195,10 @@ def test_match_min():
     # larger than one wave / one block on either side, ties between lanes and between waves: numpy's argmin
     g = np.random.default_rng(7)
     A = g.integers(0, 50, size=(333, 517)).astype(np.float32)   # (many equal entries)
-    rm, ra, cm, ca = PC.match_min(_dev(A))
+    rm, ra, cm, ca = PC.match_min(put(A))
     assert np.array_equal(ra.cpu().numpy(), A.argmin(axis=1)) and np.array_equal(rm.cpu().numpy(), A.min(axis=1))
     assert np.array_equal(ca.cpu().numpy(), A.argmin(axis=0)) and np.array_equal(cm.cpu().numpy(), A.min(axis=0))
-    r2 = PC.match_min(_dev(A))
+    r2 = PC.match_min(put(A))
     assert all(torch.equal(x, y) for x, y in zip((rm, ra, cm, ca), r2))
 
 
@@ -239,7 +220,7 @@ def test_mmd_and_cov_against_the_oracle(seed, S, R, M, N, normalize):
     sample, ref, D64 = _metric_case(seed, S, R, M, N, normalize)
     mmd64, matched64, arg64 = EO.minimum_matching_distance(D64)
     cov64, ref64, dist64 = EO.coverage(D64)
-    sd, rd = _dev(sample), _dev(ref)
+    sd, rd = put(sample), put(ref)
     mmd, matched = E.minimum_mathing_distance(sd, rd, normalize=normalize)
     cov, matched_ref, matched_dist = E.coverage(sd, rd, normalize=normalize, ret_dist=True)
     assert isinstance(mmd, float) and isinstance(cov, float)
@@ -268,7 +249,7 @@ def test_mmd_and_cov_against_the_oracle(seed, S, R, M, N, normalize):
 
 def test_identical_sets():
     E = _E()
-    x = _dev(_clouds(6, 9, 40, 55, 2024)[0])
+    x = put(_clouds(6, 9, 40, 55, 2024)[0])
     mmd, matched = E.minimum_mathing_distance(x, x)
     cov, matched_ref = E.coverage(x, x)
     assert mmd == 0.0 and not matched.any()
@@ -283,7 +264,7 @@ def test_guarded(S, R, M, N):
     value (0xFF bytes: NaN as float32, -1 as int32), the unguarded results"""
     from sivae_hip import ops, pointcloud
     from support.guard import describe, guarded
-    sample, ref = (_dev(a) for a in _clouds(S, R, M, N))
+    sample, ref = (put(a) for a in _clouds(S, R, M, N))
     D0 = pointcloud.chamfer_matrix(sample, ref)
     m0 = pointcloud.match_min(D0)
     with guarded(pointcloud) as g:  # (pointcloud's names only: its torch; `workspace` is ops' and needs ops in the list)

@@ -18,9 +18,9 @@ import torch
 
 import pc3d_jsd_oracle as JO
 import pc3d_oracle as O
+from support.pc import DEV, _PC, _np
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = [("A_sample", 28, True), ("A_ref", 28, True), ("B", 28, True), ("C", 8, False), ("E", 28, True)]
 
@@ -35,18 +35,9 @@ def _pcs(key):
     return fx[key] if key.startswith("A_") else fx[key + "_pcs"]
 
 
-def _PC():
-    from sivae_hip import pointcloud as PC
-    return PC
-
-
 def _J():
     import soft_intro_vae_3d.metrics.jsd as J
     return J
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 @pytest.mark.parametrize("key,res,clip", CASES)

@@ -12,52 +12,17 @@ Tolerances
   Parameter gradients: relative L2 against fp64, gate max(4 e32, 1e-5) per tensor with e32 the error of the fp32 run of
   the SAME restatement on the CPU (the factor 4: MFMA K-chunk order and split reductions accumulate differently).
 """
-import functools
-
 import pytest
 import torch
 
 import pc3d_oracle as O
+from support.pc import DEV, _BN, _PC, _chamfer_case, _check_indices_by_distance, _grad_report, _load, viol
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _viol(a, b, rtol=1e-4, atol_scale=1e-5):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    atol = atol_scale * float(b.abs().max())
-    return float(((a - b).abs() / (rtol * b.abs() + atol + 1e-300)).max())
-
-
-def _PC():
-    from sivae_hip import pointcloud as PC
-    return PC
 
 
 # ------------------------------------------------------------------------------------------------ Chamfer
 CHAMFER_CASES = [(2, 64, 64, 2), (3, 70, 33, 2), (2, 257, 130, 3), (2, 2048, 2048, 0), (1, 1, 5, 0)]
-
-
-@functools.lru_cache(maxsize=None)
-def _chamfer_case(B, N, M, seed):
-    """-> (preds fp32 [B, M, 3], gts fp32 [B, N, 3], fp64 pairwise distances [B, N, M], fp64 loss [B])"""
-    g = torch.Generator().manual_seed(seed)
-    gts = torch.rand(B, N, 3, generator=g, dtype=torch.float64).float()
-    preds = torch.rand(B, M, 3, generator=g, dtype=torch.float64).float()
-    P = O.pairwise_sqdist(preds.double(), gts.double())
-    return preds, gts, P, P.min(dim=1)[0].sum(1) + P.min(dim=2)[0].sum(1)
-
-
-def _check_indices_by_distance(P, idx_p, idx_g):
-    """P [B, N, M] fp64; idx_p [B, M] into the N ground-truth points, idx_g [B, N] into the M predictions"""
-    B, N, M = P.shape
-    idx_p, idx_g = idx_p.cpu().long(), idx_g.cpu().long()
-    assert idx_p.min() >= 0 and idx_p.max() < N and idx_g.min() >= 0 and idx_g.max() < M
-    dp = P.gather(1, idx_p[:, None, :])[:, 0, :]
-    dg = P.gather(2, idx_g[:, :, None])[:, :, 0]
-    mp, mg = P.min(dim=1)[0], P.min(dim=2)[0]
-    worst = max(float(((dp - mp) / mp.clamp_min(1e-300)).max()), float(((dg - mg) / mg.clamp_min(1e-300)).max()))
-    assert worst <= 1e-5, worst
 
 
 @pytest.mark.parametrize("B,N,M,seed", CHAMFER_CASES)
@@ -163,17 +128,6 @@ def test_chamfer_ties_lowest_index_and_determinism():
 
 
 # ------------------------------------------------------------------------------------------------ ReLU -> BatchNorm
-class _BN:
-    """what functional.BNState reads from a BatchNorm module"""
-
-    def __init__(self, C, training, seed):
-        g = torch.Generator().manual_seed(seed)
-        self.running_mean = (torch.rand(C, generator=g) * 0.2 - 0.1).to(DEV)
-        self.running_var = (torch.rand(C, generator=g) + 0.5).to(DEV)
-        self.num_batches_tracked = torch.tensor(3, dtype=torch.int64, device=DEV)
-        self.training, self.eps, self.momentum = training, 1e-5, 0.1
-
-
 @pytest.mark.parametrize("B,C,N", [(3, 64, 100), (2, 512, 2048), (4, 5, 1), (1, 7, 33)])
 def test_relu_bn(B, C, N):
     PC = _PC()
@@ -194,8 +148,8 @@ def test_relu_bn(B, C, N):
     gd, bd = gamma.to(DEV).requires_grad_(True), beta.to(DEV).requires_grad_(True)
     y = PC.relu_bn(ad, gd, bd, SF.BNState(bn))
     (y * dy.to(DEV)).sum().backward()
-    figs = dict(y=_viol(y, y64), rm=_viol(bn.running_mean, rm64), rv=_viol(bn.running_var, rv64),
-                da=_viol(ad.grad, a64.grad), dgamma=_viol(gd.grad, g64.grad), dbeta=_viol(bd.grad, b64.grad))
+    figs = dict(y=viol(y, y64), rm=viol(bn.running_mean, rm64), rv=viol(bn.running_var, rv64),
+                da=viol(ad.grad, a64.grad), dgamma=viol(gd.grad, g64.grad), dbeta=viol(bd.grad, b64.grad))
     print("relu_bn [%d, %d, %d]: violation ratios %s" % (B, C, N, {k: "%.3f" % v for k, v in figs.items()}))
     assert all(v <= 1.0 for v in figs.values()), figs
     assert int(bn.num_batches_tracked) == 4
@@ -206,7 +160,7 @@ def test_relu_bn(B, C, N):
     ae = a.to(DEV).requires_grad_(True)
     ye = PC.relu_bn(ae, gd, bd, SF.BNState(bn_e))
     ye64, _, _ = O.relu_bn(a.double(), gamma.double(), beta.double(), rm.double().cpu(), rv.double().cpu(), False)
-    assert _viol(ye, ye64) <= 1.0
+    assert viol(ye, ye64) <= 1.0
     assert torch.equal(bn_e.running_mean, rm) and torch.equal(bn_e.running_var, rv) and int(bn_e.num_batches_tracked) == 3
     with pytest.raises(RuntimeError, match="eval-mode BatchNorm"):
         ye.sum().backward()
@@ -237,25 +191,6 @@ def test_max_points(B, C, N):
 
 
 # ------------------------------------------------------------------------------------------------ encoder / model
-def _load(module, sd, prefix=""):
-    module.load_state_dict({k[len(prefix):]: v.detach().clone().float() for k, v in sd.items() if k.startswith(prefix)},
-                           strict=True)
-    return module.to(DEV)
-
-
-def _grad_report(name, named_params, sd64, sd32, prefix=""):
-    """per-tensor relative L2 of the GPU gradient against fp64, gated by max(4 e32, 1e-5)"""
-    bad = []
-    for k, p in named_params:
-        ref = sd64[prefix + k].grad
-        e_gpu, e32 = O.rel_l2(p.grad, ref), O.rel_l2(sd32[prefix + k].grad, ref)
-        gate = max(4 * e32, 1e-5)
-        print("%s grad %-28s gpu %.3e  cpu-fp32 %.3e  gate %.3e" % (name, k, e_gpu, e32, gate))
-        if not e_gpu <= gate:
-            bad.append((k, e_gpu, gate))
-    assert not bad, bad
-
-
 @pytest.mark.parametrize("B,N", [(3, 100), (2, 2048)])
 def test_encoder(B, N):
     import soft_intro_vae_3d.models.vae as V
@@ -275,12 +210,12 @@ def test_encoder(B, N):
     enc = _load(V.Encoder(O.config(z)), sd64).train()
     mu, lv = enc(x.to(DEV))
     ((mu * r1.to(DEV)).sum() + (lv * r2.to(DEV)).sum()).backward()
-    v_mu, v_lv = _viol(mu, mu64), _viol(lv, lv64)
+    v_mu, v_lv = viol(mu, mu64), viol(lv, lv64)
     print("encoder B=%d N=%d: mu %.3f logvar %.3f of the element-wise criterion" % (B, N, v_mu, v_lv))
     assert v_mu <= 1.0 and v_lv <= 1.0
     for k, v in upd64.items():
         got = enc.state_dict()[k]
-        assert (_viol(got, v) <= 1.0) if v.is_floating_point() else (int(got) == int(v)), k
+        assert (viol(got, v) <= 1.0) if v.is_floating_point() else (int(got) == int(v)), k
     _grad_report("encoder[%d,%d]" % (B, N), enc.named_parameters(), sd64, runs[torch.float32][0])
 
 
@@ -323,7 +258,7 @@ def test_model_vae_objective_and_adam_steps():
         out32 = O.vae_objective(sd32, x, eps, update=upd)
         out32["loss"].backward()
         if step == 0:
-            figs = {k: _viol(out[k], out64[k]) for k in ("mu", "logvar", "rec", "chamfer", "kl", "loss")}
+            figs = {k: viol(out[k], out64[k]) for k in ("mu", "logvar", "rec", "chamfer", "kl", "loss")}
             print("model: violation ratios vs fp64 %s" % {k: "%.3f" % v for k, v in figs.items()})
             assert all(v <= 1.0 for v in figs.values()), figs
             _grad_report("model", model.named_parameters(), sd64, sd32)
@@ -352,13 +287,13 @@ def test_bootstrap_and_no_batchnorm_forward():
     for use_target, prefix in ((True, "target_decoder."), (False, "decoder.")):
         model.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)  # (fresh BatchNorm buffers per pass)
         y, mu, lv = model(x.to(DEV), deterministic=True, use_target_decoder=use_target)
-        assert _viol(mu, mu64) <= 1.0 and _viol(lv, lv64) <= 1.0
-        assert _viol(y, O.decoder(sd, mu64, prefix=prefix)) <= 1.0
-        assert _viol(model.sample(mu, use_target_decoder=use_target), O.decoder(sd, mu64, prefix=prefix)) <= 1.0
+        assert viol(mu, mu64) <= 1.0 and viol(lv, lv64) <= 1.0
+        assert viol(y, O.decoder(sd, mu64, prefix=prefix)) <= 1.0
+        assert viol(model.sample(mu, use_target_decoder=use_target), O.decoder(sd, mu64, prefix=prefix)) <= 1.0
     assert not torch.equal(model.decode(mu), model.decode_target(mu))
     for use_bias in (True, False):
         sdn = O.recipe_state_dict(O.encoder_specs(z, bn=False, use_bias=use_bias), 13, torch.float64)
         enc = _load(V.EncoderNoBatchNorm(O.config(z, use_bias_e=use_bias)), sdn)
         mu, lv = enc(x.to(DEV))
         m64, l64 = O.encoder(sdn, x.double(), bn=False)
-        assert _viol(mu, m64) <= 1.0 and _viol(lv, l64) <= 1.0
+        assert viol(mu, m64) <= 1.0 and viol(lv, l64) <= 1.0

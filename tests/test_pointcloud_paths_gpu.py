@@ -21,28 +21,9 @@ import torch
 
 import pc3d_jsd_oracle as JO
 import pc3d_oracle as O
-from test_pointcloud_gpu import _BN, _chamfer_case, _check_indices_by_distance, _viol
+from support.pc import DEV, _BN, _PC, _chamfer_case, _check_indices_by_distance, _np, put, viol
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _PC():
-    from sivae_hip import pointcloud as PC
-    return PC
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _misaligned(t):
-    """a contiguous device copy of t that is 4-byte but not 16-byte aligned: carved one element into a larger buffer"""
-    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=DEV)
-    v = buf[1:1 + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
 
 
 # ------------------------------------------------------------------------------------------------ ReLU -> BatchNorm
@@ -83,7 +64,7 @@ def _relu_bn_check(label, a, gamma, beta, dy, put_a=lambda t: t.to(DEV)):
     y = PC.relu_bn(ad, gd, bd, SF.BNState(bn))
     (y * dy.to(DEV)).sum().backward()
     got = dict(y=y, rm=bn.running_mean, rv=bn.running_var, da=ad.grad, dgamma=gd.grad, dbeta=bd.grad)
-    figs = {k: _viol(got[k], ref[k]) for k in ref}
+    figs = {k: viol(got[k], ref[k]) for k in ref}
     print("relu_bn %s %s: violation ratios %s" % (label, tuple(a.shape), {k: "%.3f" % v for k, v in figs.items()}))
     assert all(v <= 1.0 for v in figs.values()), figs
     assert int(bn.num_batches_tracked) == 4
@@ -118,12 +99,12 @@ def test_relu_bn_misaligned(B, C, N):
     PC = _PC()
     assert N % 4 == 0
     a, gamma, beta, dy = _relu_bn_inputs(B, C, N)
-    got, ref = _relu_bn_check("misaligned a", a, gamma, beta, dy, put_a=_misaligned)
-    ad, dyd = a.to(DEV), _misaligned(dy)
+    got, ref = _relu_bn_check("misaligned a", a, gamma, beta, dy, put_a=functools.partial(put, misaligned=True))
+    ad, dyd = a.to(DEV), put(dy, misaligned=True)
     assert ad.data_ptr() % 16 == 0 and dyd.data_ptr() % 16 == 4
     mean, invstd = PC.relu_bn_stats(ad)
     da, dgamma, dbeta = PC.relu_bn_bwd(dyd, ad, mean, invstd, gamma.to(DEV))
-    figs = dict(da=_viol(da, ref["da"]), dgamma=_viol(dgamma, ref["dgamma"]), dbeta=_viol(dbeta, ref["dbeta"]))
+    figs = dict(da=viol(da, ref["da"]), dgamma=viol(dgamma, ref["dgamma"]), dbeta=viol(dbeta, ref["dbeta"]))
     print("relu_bn_bwd misaligned dy %s: violation ratios %s" % ((B, C, N), {k: "%.3f" % v for k, v in figs.items()}))
     assert all(v <= 1.0 for v in figs.values()), figs
     assert bool((da[ad == 0] == 0).all()) and bool((da[:, 0] == 0).all())
@@ -155,7 +136,7 @@ def test_relu_bn_propagates_nan():
         figs = {}
         for k, v in got.items():
             dim = 1 if v.dim() == 3 else 0
-            figs[k] = _viol(v.detach().cpu().index_select(dim, keep), ref[k].index_select(dim, keep))
+            figs[k] = viol(v.detach().cpu().index_select(dim, keep), ref[k].index_select(dim, keep))
         print("relu_bn with a NaN %s: violation ratios of the other channels %s"
               % ((B, C, N), {k: "%.3f" % v for k, v in figs.items()}))
         assert all(v <= 1.0 for v in figs.values()), figs
@@ -212,7 +193,7 @@ def test_max_points_scalar_path(B, C, N, k):
 def test_max_points_misaligned():
     """N % 4 == 0 with x 4 bytes off a 16-byte boundary: the scalar kernel"""
     x = _max_points_rows(3, 5, 132, 1)
-    vals, arg = _max_points_check(x, put=_misaligned)
+    vals, arg = _max_points_check(x, put=functools.partial(put, misaligned=True))
     assert arg.view(-1).tolist()[:5] == [0, 5, 0, 3, 131]
 
 
@@ -479,7 +460,7 @@ def test_pointwise_conv_one_row_maps(B, Ci, Co, N, with_bias, relu):
     y = PC.pointwise_conv(xd, wd, bd, relu=relu)
     assert y.shape == (B, Co, N)
     (y * dy.to(DEV)).sum().backward()
-    v = _viol(y, ref["y"])
+    v = viol(y, ref["y"])
     print("  y: %.3f of the element-wise criterion" % v)
     assert v <= 1.0
     bad = []

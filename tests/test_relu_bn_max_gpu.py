@@ -15,9 +15,9 @@ smallest: every a <= 0 of the row ties), gamma[2] == 0 exactly (all y equal beta
 allows, the last row has its maximum at two indices of one lane and at one index of another lane (16-byte path: a lane
 owns 4 i .. 4 i + 3; scalar path: i and i + 64).
 
-Forward values and indices are compared with torch.equal: the fused kernel forms y with the operations of
-relu_bn_apply_kernel (one multiply for gamma invstd, one FMA for the shift, one FMA per element), so nothing may differ.
-Element-wise gate: |x - ref| <= 1e-4 |ref| + 1e-5 max|ref| (test_pointcloud_gpu._viol <= 1).  dgamma / dbeta against
+Forward values and indices are compared with torch.equal: the fused kernel forms y with the function relu_bn_apply_kernel
+stores (one multiply for gamma invstd, one FMA for the shift, one FMA per element), so nothing may differ.
+Element-wise gate: |x - ref| <= 1e-4 |ref| + 1e-5 max|ref| (support.pc.viol <= 1).  dgamma / dbeta against
 fp64: relative L2 <= max(4 e32, 1e-5), e32 the error of the fp32 run of the same restatement on the CPU.
 """
 import functools
@@ -26,29 +26,12 @@ import pytest
 import torch
 
 import pc3d_oracle as O
-from test_pointcloud_gpu import _BN, _grad_report, _load, _viol
+from support.pc import DEV, _BN, _PC, _grad_report, _load, put, viol
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 CASES = [(3, 5, 100, False), (2, 3, 33, False), (1, 7, 1, False), (2, 6, 260, False), (2, 5, 2048, False),
          (3, 5, 132, True)]
 EPS = 1e-5
-
-
-def _PC():
-    from sivae_hip import pointcloud as PC
-    return PC
-
-
-def _put(t, misaligned=False):
-    """device copy of t; misaligned: 4 bytes behind a 16-byte boundary (carved one element into a larger buffer)"""
-    if not misaligned:
-        return t.to(DEV)
-    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=DEV)
-    v = buf[1:1 + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
 
 
 def _dup_indices(N, vec):
@@ -84,7 +67,7 @@ def _case(B, C, N, misaligned):
 
 def _device(case, misaligned):
     PC = _PC()
-    a = _put(case["a"], misaligned)
+    a = put(case["a"], misaligned)
     gamma, beta = case["gamma"].to(DEV), case["beta"].to(DEV)
     mean, invstd = PC.relu_bn_stats(a)
     return a, gamma, beta, mean, invstd
@@ -109,7 +92,7 @@ def test_forward_equals_the_composition_bit_for_bit(B, C, N, misaligned):
     assert bool((i1[:, 0] == 0).all()) and bool((i1[:, 2] == 0).all())  # all-equal rows: index 0
     # against fp64
     v_t, _ = PC.relu_bn_max_fwd(a, mean, invstd, gamma, beta)
-    figs = dict(train=_viol(v_t, case["vals64"]), eval=_viol(v1, case["vals64_eval"]))
+    figs = dict(train=viol(v_t, case["vals64"]), eval=viol(v1, case["vals64_eval"]))
     print("relu_bn_max fwd [%d, %d, %d]: violation ratios vs fp64 %s" % (B, C, N, {k: "%.3f" % v for k, v in figs.items()}))
     assert all(v <= 1.0 for v in figs.values()), figs
 
@@ -123,8 +106,8 @@ def test_autograd_function_equals_the_composition(B, C, N, misaligned):
     gamma, beta = case["gamma"].to(DEV), case["beta"].to(DEV)
     for training in (True, False):
         bn0, bn1 = _BN(C, training, 5), _BN(C, training, 5)
-        out0 = PC.max_points(PC.relu_bn(_put(case["a"], misaligned), gamma, beta, SF.BNState(bn0)))
-        out1 = PC.relu_bn_max(_put(case["a"], misaligned), gamma, beta, SF.BNState(bn1))
+        out0 = PC.max_points(PC.relu_bn(put(case["a"], misaligned), gamma, beta, SF.BNState(bn0)))
+        out1 = PC.relu_bn_max(put(case["a"], misaligned), gamma, beta, SF.BNState(bn1))
         assert torch.equal(out1, out0)
         assert torch.equal(bn1.running_mean, bn0.running_mean) and torch.equal(bn1.running_var, bn0.running_var)
         assert int(bn1.num_batches_tracked) == int(bn0.num_batches_tracked) == (4 if training else 3)
@@ -154,7 +137,7 @@ def test_backward(B, C, N, misaligned):
     # fp64, the kernel's own indices
     da64, dg64, db64 = _fp64_backward(case, arg, torch.float64)
     _, dg32, db32 = _fp64_backward(case, arg, torch.float32)
-    v_da = _viol(da, da64)
+    v_da = viol(da, da64)
     print("relu_bn_max bwd [%d, %d, %d]: da %.3f of the element-wise criterion" % (B, C, N, v_da))
     assert v_da <= 1.0
     for name, got, ref, r32 in (("dgamma", dgamma, dg64, dg32), ("dbeta", dbeta, db64, db32)):
@@ -164,7 +147,7 @@ def test_backward(B, C, N, misaligned):
         assert e_gpu <= max(4 * e32, 1e-5), (name, e_gpu, e32)
     # the composition's backward on the same g and arg
     da_c, dg_c, db_c = PC.relu_bn_bwd(PC.max_points_bwd(gy, arg, N), a, mean, invstd, gamma)
-    figs = dict(da=_viol(da, da_c), dgamma=_viol(dgamma, dg_c), dbeta=_viol(dbeta, db_c))
+    figs = dict(da=viol(da, da_c), dgamma=viol(dgamma, dg_c), dbeta=viol(dbeta, db_c))
     print("relu_bn_max bwd [%d, %d, %d]: violation ratios vs the composition %s"
           % (B, C, N, {k: "%.3f" % v for k, v in figs.items()}))
     assert all(v <= 1.0 for v in figs.values()), figs
@@ -179,7 +162,7 @@ def test_backward(B, C, N, misaligned):
     assert torch.equal(da2, da) and torch.equal(dgamma2, dgamma) and torch.equal(dbeta2, dbeta)
     # through autograd
     from sivae_hip import functional as SF
-    ad = _put(case["a"], misaligned).requires_grad_(True)
+    ad = put(case["a"], misaligned).requires_grad_(True)
     gd, bd = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     out = PC.relu_bn_max(ad, gd, bd, SF.BNState(_BN(C, True, 5)))
     assert torch.equal(out, vals)
