@@ -603,11 +603,12 @@ def _prologue(pro):
     return _p(pm), _p(pi), _p(pg), _p(pb), float(slope)
 
 
-def _conv_call(r, a, b, c, dims, ks=0, bias=None, pro=None, stats=None, upsample=False, accumulate=False, seg=0):
+def _conv_call(r, a, b, c, dims, ks=0, bias=None, pro=None, stats=None, upsample=False, accumulate=False, seg=0,
+               out_f32=False):
     """the one launch of a conv route.  Every conv entry point takes a subset of the same arguments in the same order —
     three tensors, [b]ias, [P]rologue + slope, [S]tatistics, the five sizes ([h]: the map halved, [f]: H * W as one),
-    [k]ernel size, [u]psample flag, [a]ccumulate flag, se[g]ment images, [w]orkspace + its size, stream — and r.args
-    names the subset."""
+    [k]ernel size, [u]psample flag, [a]ccumulate flag, fp32 NCHW [o]utput flag (bf16 mode), se[g]ment images,
+    [w]orkspace + its size, stream — and r.args names the subset."""
     s = r.args
     args = [_p(a), _p(b), _p(c)]
     if "b" in s:
@@ -624,6 +625,8 @@ def _conv_call(r, a, b, c, dims, ks=0, bias=None, pro=None, stats=None, upsample
         args.append(int(bool(upsample)))
     if "a" in s:
         args.append(int(bool(accumulate)))
+    if "o" in s:
+        args.append(int(bool(out_f32)))
     if "g" in s:
         args.append(seg)
     if "w" in s:

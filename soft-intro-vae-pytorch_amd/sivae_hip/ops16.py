@@ -5,6 +5,12 @@ Activations are torch.bfloat16 tensors of shape [B, C16/8, H, W, 8] ("blocked NC
 vector, channel count padded to a multiple of 16 with zeros — bf16_common.h).  Statistics, BatchNorm parameters and their
 gradients, weights and weight gradients are float32.  Like `ops`, everything launches on torch's current stream of the
 tensor's device and there is no CPU path.
+
+Like `ops`, the module is route functions (*_route -> ops.Route: WHICH entry point, split-K factor, statistics rows,
+workspace and timer key a layer gets, from integers and flags alone — only they ask the sivae_bf16_* predicates) and
+launch functions that allocate and marshal what the route names.  tests/test_conv_routes_host.py holds the routes to a
+recording of the dispatch they replaced (tests/golden/conv_routes_bf16.json.gz): a new bf16 kernel path is a new Route
+value here plus that fixture regenerated, and nothing else.
 """
 import os
 import sys
@@ -16,7 +22,6 @@ from . import ops
 
 _p, _s = ops._p, ops._s
 LRELU_SLOPE = ops.LRELU_SLOPE
-TIMER_KEYS = True
 
 
 # SIVAE_BF16_POOL_DGRAD=0: the data gradient of a conv of an upsampled input is written at full resolution and summed by
@@ -111,6 +116,60 @@ class PackedW16:
         _lib.call("sivae_bf16_pack_conv_weight", _p(w), _p(self.data), Co, Ci, ks, mode, _s(w))
 
 
+@ops._memo
+def conv2d_route(B, Ci, Co, H, W, ks, *, bias=False, out_f32=False, want_stats=False):
+    """route of conv2d for a [B, Co, H, W] OUTPUT map: plain, or split-K on small grids (3x3, bf16 output, no bias)"""
+    L = _lib.load()
+    key = "bf16_conv_kernel<%d,%s>" % (ks, "co32" if Co <= 32 else ("co64" if Co <= 64 else "co128"))  # (tile class)
+    S = L.sivae_bf16_conv2d_splitk(B, Ci, Co, H, W, ks) if (ks == 3 and not out_f32 and not bias) else 1
+    if S > 1:
+        return ops.Route("splitk", "sivae_bf16_conv2d_fwd_splitk", None, "PSkuaw", split=S, key=key,
+                         stats_rows=L.sivae_bf16_conv2d_splitk_stats_rows(B, Ci, Co, H, W, ks) if want_stats else 0,
+                         ws_bytes=L.sivae_bf16_conv2d_splitk_workspace_bytes(B, Ci, Co, H, W, ks))
+    return ops.Route("plain", "sivae_bf16_conv2d_fwd", None, "bPSkuao", key=key,
+                     stats_rows=L.sivae_bf16_conv2d_num_px_tiles(B, Co, H, W, ks) if want_stats else 0)
+
+
+@ops._memo
+def conv2d_pool_route(B, Ci, Co, H, W, ks=3):
+    """route of conv2d_pool for x [B, Ci, H, W]: 3x3, even maps, and a grid that fills the chip without a K split (the
+    small 512-channel maps keep conv2d + upsample2_bwd, whose split-K form has no pooled epilogue).  `error` is the
+    PLANNER's refusal (conv2d_pool_supported); conv2d_pool itself launches what it is handed."""
+    r = conv2d_route(B, Ci, Co, H, W, 3)  # (the same kernel with another epilogue: its split-K decision, its timer key)
+    ok = POOL_DGRAD and ks == 3 and H % 2 == 0 and W % 2 == 0 and r.split == 1
+    return ops.Route("pool", "sivae_bf16_conv2d_fwd_pool", None, "a", key=r.key,
+                     error=None if ok else (ValueError, "sivae_hip: no pooled data gradient for this layer"))
+
+
+def conv2d_pool_supported(B, Ci, Co, H, W, ks):
+    return conv2d_pool_route(B, Ci, Co, H, W, ks).error is None
+
+
+@ops._memo
+def conv2d_wgrad_route(B, Ci, Co, H, W, ks):
+    return ops.Route("wgrad", "sivae_bf16_conv2d_wgrad", None, "Pkuw", key="bf16_wgrad_kernel<%d>" % ks,
+                     ws_bytes=_lib.load().sivae_bf16_conv2d_wgrad_workspace_bytes(B, Ci, Co, H, W, ks))
+
+
+def bn_bwd_route(B, C, H, W, *, nseg=1):
+    """route of bn_bwd: one launch that reads dy and x once (bf16_bn_fused.hip), or the three-launch form per segment
+    (maps the one-launch form does not take, synchronised BatchNorm, two ranks on one device: read at call time)"""
+    fused, three = _bn_bwd_routes(B, C, H, W, nseg)
+    if fused and ops.BN_FUSED and ops.SYNC_BN is None and os.environ.get("SIVAE_DP_SAME_DEVICE", "0") != "1":
+        return fused
+    return three
+
+
+@ops._memo
+def _bn_bwd_routes(B, C, H, W, nseg):
+    """(the one-launch route, or None where the library does not take the shape; the three-launch route)"""
+    L = _lib.load()
+    fused = ops.Route("bn_fused", "sivae_bf16_bn_bwd_fused_seg",
+                      ws_bytes=L.sivae_bf16_bn_bwd_fused_seg_workspace_bytes(B, C, H, W, B // nseg))
+    return (fused if L.sivae_bf16_bn_bwd_fused_seg_supported(B, C, H, W, B // nseg) == 1 else None,
+            ops.Route("bn_three", "sivae_bf16_bn_bwd", ws_bytes=L.sivae_bf16_bn_bwd_workspace_bytes(B // nseg, C, H, W)))
+
+
 def conv2d(x, wp, Ci, Co, ks, bias=None, pro=None, upsample=False, want_stats=False, out=None, accumulate=False,
            out_f32=False):
     """x blocked [B, Cib, Hs, Ws, 8] -> y blocked [B, Cob, H, W, 8] (or fp32 NCHW [B, Co, H, W] with out_f32).
@@ -120,41 +179,16 @@ def conv2d(x, wp, Ci, Co, ks, bias=None, pro=None, upsample=False, want_stats=Fa
     B, Cib, Hs, Ws, _ = x.shape
     assert Cib == cblocks(Ci), (Cib, Ci)
     H, W = (2 * Hs, 2 * Ws) if upsample else (Hs, Ws)
-    L = _lib.load()
-    if out is not None:
-        y = out
-    elif out_f32:
-        y = torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-    else:
-        y = empty_blocked(B, Co, H, W, x.device)
-    splitk = (ks == 3 and not out_f32 and bias is None
-              and L.sivae_bf16_conv2d_splitk(B, Ci, Co, H, W, ks) > 1)  # small grids: split the input-channel range
-    stats = None
-    if want_stats:
-        rows = (L.sivae_bf16_conv2d_splitk_stats_rows(B, Ci, Co, H, W, ks) if splitk
-                else L.sivae_bf16_conv2d_num_px_tiles(B, Co, H, W, ks))
-        stats = torch.empty((rows, Co, 2), dtype=torch.float32, device=x.device)
-    pm, pi, pg, pb, slope = ops._prologue(pro)
+    r = conv2d_route(B, Ci, Co, H, W, ks, bias=bias is not None, out_f32=bool(out_f32), want_stats=bool(want_stats))
+    y = out if out is not None else (torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device) if out_f32
+                                     else empty_blocked(B, Co, H, W, x.device))
+    stats = torch.empty((r.stats_rows, Co, 2), dtype=torch.float32, device=x.device) if want_stats else None
     ops._require(bias)
     t0 = ops.timer_begin()
-    if splitk:
-        ws = ops.workspace(L.sivae_bf16_conv2d_splitk_workspace_bytes(B, Ci, Co, H, W, ks), x.device)
-        _lib.call("sivae_bf16_conv2d_fwd_splitk", _p(x), _p(wp.data), _p(y), pm, pi, pg, pb, slope, _p(stats), B, Ci,
-                  Co, H, W, ks, int(bool(upsample)), int(bool(accumulate)), _p(ws), ws.numel(), _s(x))
-    else:
-        _lib.call("sivae_bf16_conv2d_fwd", _p(x), _p(wp.data), _p(y), _p(bias), pm, pi, pg, pb, slope, _p(stats), B,
-                  Ci, Co, H, W, ks, int(bool(upsample)), int(bool(accumulate)), int(bool(out_f32)), _s(x))
+    ops._conv_call(r, x, wp.data, y, (B, Ci, Co, H, W), ks, bias, pro, stats, upsample, accumulate, 0, out_f32)
     if t0 is not None:
-        ops.timer_end(t0, "bf16_conv_kernel<%d,%s>" % (ks, "co32" if Co <= 32 else ("co64" if Co <= 64 else "co128")),
-                      2.0 * B * H * W * Co * Ci * _taps(ks))
+        ops.timer_end(t0, r.key, 2.0 * B * H * W * Co * Ci * _taps(ks))
     return (y, stats) if want_stats else y
-
-
-def conv2d_pool_supported(B, Ci, Co, H, W, ks):
-    """can conv2d_pool take this layer?  (3x3, even maps, and the grid fills the chip without a K split: the small
-    512-channel maps keep conv2d + upsample2_bwd, whose split-K form has no pooled epilogue)"""
-    return (POOL_DGRAD and ks == 3 and H % 2 == 0 and W % 2 == 0
-            and _lib.load().sivae_bf16_conv2d_splitk(B, Ci, Co, H, W, ks) <= 1)
 
 
 def conv2d_pool(x, wp, Ci, Co, out=None, accumulate=False):
@@ -166,11 +200,11 @@ def conv2d_pool(x, wp, Ci, Co, out=None, accumulate=False):
     assert Cib == cblocks(Ci), (Cib, Ci)
     y = out if out is not None else empty_blocked(B, Co, H // 2, W // 2, x.device)
     assert tuple(y.shape) == (B, cblocks(Co), H // 2, W // 2, 8)
+    r = conv2d_pool_route(B, Ci, Co, H, W)
     t0 = ops.timer_begin()
-    _lib.call("sivae_bf16_conv2d_fwd_pool", _p(x), _p(wp.data), _p(y), B, Ci, Co, H, W, int(bool(accumulate)), _s(x))
+    ops._conv_call(r, x, wp.data, y, (B, Ci, Co, H, W), accumulate=accumulate)
     if t0 is not None:
-        ops.timer_end(t0, "bf16_conv_kernel<3,%s>" % ("co32" if Co <= 32 else ("co64" if Co <= 64 else "co128")),
-                      2.0 * B * H * W * Co * Ci * 9)
+        ops.timer_end(t0, r.key, 2.0 * B * H * W * Co * Ci * 9)
     return y
 
 
@@ -179,15 +213,12 @@ def conv2d_wgrad(x, dy, Ci, Co, ks, pro=None, upsample=False, out=None):
     _req16(x, dy)
     B, Cob, H, W, _ = dy.shape
     assert Cob == cblocks(Co) and x.shape[1] == cblocks(Ci)
-    L = _lib.load()
-    ws = ops.workspace(L.sivae_bf16_conv2d_wgrad_workspace_bytes(B, Ci, Co, H, W, ks), x.device)
+    r = conv2d_wgrad_route(B, Ci, Co, H, W, ks)
     dw = ops._out(out, (Co, Ci, 5, 1) if ks == KS51 else (Co, Ci, ks, ks), x.device)
-    pm, pi, pg, pb, slope = ops._prologue(pro)
     t0 = ops.timer_begin()
-    _lib.call("sivae_bf16_conv2d_wgrad", _p(x), _p(dy), _p(dw), pm, pi, pg, pb, slope, B, Ci, Co, H, W, ks,
-              int(bool(upsample)), _p(ws), ws.numel(), _s(x))
+    ops._conv_call(r, x, dy, dw, (B, Ci, Co, H, W), ks, None, pro, None, upsample)
     if t0 is not None:
-        ops.timer_end(t0, "bf16_wgrad_kernel<%d>" % ks, 2.0 * B * H * W * Co * Ci * _taps(ks))
+        ops.timer_end(t0, r.key, 2.0 * B * H * W * Co * Ci * _taps(ks))
     return dw
 
 
@@ -239,19 +270,15 @@ def bn_bwd(dy, y, x, mean, invstd, gamma, beta, C, slope=LRELU_SLOPE, dy_pooled=
     elif want_dz:
         dz = torch.empty_like(x)
     dgamma, dbeta = ops._pg(pg_out, C, x.device, want_param_grads)
-    L = _lib.load()
-    if (ops.BN_FUSED and ops.SYNC_BN is None and os.environ.get("SIVAE_DP_SAME_DEVICE", "0") != "1"
-            and L.sivae_bf16_bn_bwd_fused_seg_supported(B, C, H, W, bs) == 1):
-        # one launch, dy and x read once (bf16_bn_fused.hip)
-        ws = ops.workspace(L.sivae_bf16_bn_bwd_fused_seg_workspace_bytes(B, C, H, W, bs), x.device)
+    r = bn_bwd_route(B, C, H, W, nseg=nseg)
+    ws = ops.workspace(r.ws_bytes, x.device)
+    if r.family == "bn_fused":
         _lib.call("sivae_bf16_bn_bwd_fused_seg", _p(dy), int(bool(dy_pooled)), _p(y), _p(mask), _p(x), _p(mean),
                   _p(invstd), _p(gamma), _p(beta), float(slope), _p(dx), _p(dz), int(bool(dz_sum)), _p(dgamma),
                   _p(dbeta), B, C, H, W, bs, _p(ops.bn_fused_state(x.device)), _p(ws), ws.numel(), _s(x))
         return dx, dz, dgamma, dbeta
-    # three-launch form (maps the one-launch form does not take, synchronised BatchNorm, two ranks on one device): a
-    # segment is a contiguous run of images, so a segmented batch is nseg calls on its slices; dgamma / dbeta are the
-    # segments' sums added in segment order
-    ws = ops.workspace(L.sivae_bf16_bn_bwd_workspace_bytes(bs, C, H, W), x.device)
+    # three-launch form: a segment is a contiguous run of images, so a segmented batch is nseg calls on its slices;
+    # dgamma / dbeta are the segments' sums added in segment order
     for g in range(nseg):
         sl = slice(g * bs, (g + 1) * bs)
         pg = nseg > 1 and g > 0 and dgamma is not None

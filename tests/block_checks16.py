@@ -27,8 +27,8 @@ many of those actually differ from the fp64 sign ("flips").
 
 Every block case runs through sivae_hip.nn.ResidualBlock on a blocked bf16 input, the stem / predict cases through
 functional16.stem / conv_bias: the real dispatch.  `block_route` / `production_routes` give the route class of a block
-from the library's own predicates; tests/test_block_routes16_host.py checks that every class the benchmarked bf16
-iterations take is covered by a case here.
+from the route functions of ops16 — the code that launches; tests/test_block_routes16_host.py checks that every class
+the benchmarked bf16 iterations take is covered by a case here.
 Used by tests/test_blocks16_gpu.py (pytest -m gpu) and `python tests/block_checks16.py [filter...]`.
 """
 import os
@@ -194,30 +194,29 @@ def ref_block(x, P, st1, st2, x_up, post, training, ties, hip1=None, hip2=None):
 
 
 # ---- route classes ---------------------------------------------------------------------------------------------------
-def _tile(L, B, Ci, Co, H, W):
+def _tile(ops16, B, Ci, Co, H, W):
     """pixel tile of a 3x3 forward conv: 'splitk' (K-split partials, one statistics row per image), 'big', 'small'"""
-    if L.sivae_bf16_conv2d_splitk(B, Ci, Co, H, W, 3) > 1:
-        return "splitk"
-    n = L.sivae_bf16_conv2d_num_px_tiles(B, Co, H, W, 3)
-    return "big" if B * H * W // n > (128 if Co > 64 else 256) else "small"
+    r = ops16.conv2d_route(B, Ci, Co, H, W, 3, want_stats=True)
+    return "splitk" if r.split > 1 else ("big" if B * H * W // r.stats_rows > (128 if Co > 64 else 256) else "small")
 
 
 def block_route(B, nseg, Ci, Cm, Co, H, W, x_up, post, bn_fused=True, pool_dgrad=True):
-    """route class of a ResidualBlock call from the library's predicates:
+    """route class of a ResidualBlock call, asked of the route functions of ops16 and the block plan under the case's
+    own switches (as check_block sets them):
     (has_exp, x_up, post, conv1 tile, conv2 tile, pooled data gradient (x_up only), BN-1 / BN-2 one-launch backward,
     segmented)"""
     from sivae_hip import functional16 as SF16
-    from sivae_hip import lib
-    L = lib.load()
-    seg = B // nseg
-    pool = None
-    if x_up:
-        plan = SF16.resblock_plan16(B, Ci, Cm, Co, H, W, x_up=x_up, post=post, nseg=nseg, has_exp=Ci != Co, training=True)
-        pool = bool(pool_dgrad and plan.dx == "pool")
-    f1 = bool(bn_fused and L.sivae_bf16_bn_bwd_fused_seg_supported(B, Cm, H, W, seg) == 1)
-    f2 = bool(bn_fused and L.sivae_bf16_bn_bwd_fused_seg_supported(B, Co, H, W, seg) == 1)
-    return ("block", Ci != Co, bool(x_up), post, _tile(L, B, Ci, Cm, H, W), _tile(L, B, Cm, Co, H, W), pool, f1, f2,
-            nseg > 1)
+    from sivae_hip import ops, ops16
+    saved = (ops.BN_FUSED, ops16.POOL_DGRAD)
+    ops.BN_FUSED, ops16.POOL_DGRAD = bn_fused, saved[1] and pool_dgrad
+    try:
+        pool = x_up and SF16.resblock_plan16(B, Ci, Cm, Co, H, W, x_up=x_up, post=post, nseg=nseg, has_exp=Ci != Co,
+                                             training=True).dx == "pool"
+        f1, f2 = (ops16.bn_bwd_route(B, C, H, W, nseg=nseg).family == "bn_fused" for C in (Cm, Co))
+        return ("block", Ci != Co, bool(x_up), post, _tile(ops16, B, Ci, Cm, H, W), _tile(ops16, B, Cm, Co, H, W),
+                pool if x_up else None, f1, f2, nseg > 1)
+    finally:
+        ops.BN_FUSED, ops16.POOL_DGRAD = saved
 
 
 def walk_routes(channels, image_size, B, nseg=1, cdim=3, convs=None):

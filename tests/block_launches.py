@@ -12,10 +12,10 @@ records, per Function call:
   grads       the None / (shape, dtype) pattern of the backward's return tuple
   raise       the exception type and message where the call is refused
 
-The recorder additions live here, not in the package: `ops16` binds `_p` / `_s` at import and has its own `_req16`;
-`ops._ld` asks for a device tensor; the sign-mask backwards check `mask.is_cuda` (they are handed a stand-in); and a
-meta tensor's data_ptr() is 0, so while recording meta tensors answer with a storage identity instead (the replay
-caches and the pack caches compare data_ptr()).
+The recorder additions live here, not in the package (what `ops16` needs is in conv_routes.recording, which the bf16
+dispatch recording shares): `ops._ld` asks for a device tensor; the sign-mask backwards check `mask.is_cuda` (they are
+handed a stand-in); and a meta tensor's data_ptr() is 0, so while recording meta tensors answer with a storage identity
+instead (the replay caches and the pack caches compare data_ptr()).
 
     python tests/block_launches.py            # writes tests/golden/block_launches.json.gz
     python tests/block_launches.py --trace    # also lists the lines of the block Functions that never ran
@@ -40,19 +40,6 @@ FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bl
 # the switches of the glue, set explicitly like conv_routes.SWITCHES (module name -> {switch: value})
 GLUE = dict(functional=dict(MATERIALIZE_H=False, DIRECT_GRADS=True), nn=dict(DEFER_UPSAMPLE=True),
             functional16=dict(MATERIALIZE_H=True, SIGNMASK=True, KWPACK=True), ops16=dict(POOL_DGRAD=True))
-
-
-class _MaskOf(CR._Mask):
-    """conv_routes._Mask with the size of the meta tensor it stands for"""
-
-    def __init__(self, t):
-        self.n = t.numel()
-
-    def numel(self):
-        return self.n
-
-    def __getitem__(self, sl):
-        return self
 
 
 def _desc(t):
@@ -149,14 +136,11 @@ def recording(switches=None, glue=None):
             for mname, sw in GLUE.items():
                 for k, v in dict(sw, **(glue or {}).get(mname, {})).items():
                     patch(mods[mname], k, v)
-            patch(ops16, "_p", ops._p)
-            patch(ops16, "_s", ops._s)
-            patch(ops16, "_req16", lambda *tensors: None)
             patch(ops, "_ld", lambda t: t.stride(0))
             signmask, bn_bwd16, ptr, apply_ = ops.bn_bwd_signmask, ops16.bn_bwd, torch.Tensor.data_ptr, SF._apply
-            patch(ops, "bn_bwd_signmask", lambda dy, mask, *a, **k: signmask(dy, _MaskOf(mask), *a, **k))
+            patch(ops, "bn_bwd_signmask", lambda dy, mask, *a, **k: signmask(dy, CR._MaskOf(mask), *a, **k))
             patch(ops16, "bn_bwd", lambda dy, y, *a, **k: bn_bwd16(
-                dy, _MaskOf(y) if (y is not None and y.dtype == torch.uint8) else y, *a, **k))
+                dy, CR._MaskOf(y) if (y is not None and y.dtype == torch.uint8) else y, *a, **k))
             patch(torch.Tensor, "data_ptr", lambda t: _meta_ptr(t) if t.device.type == "meta" else ptr(t))
             patch(SF, "_apply", lambda fn, *args: sess.run(fn, lambda: apply_(fn, *args)))
             for fn in _functions(SF, SF16):

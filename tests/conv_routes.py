@@ -18,6 +18,14 @@ The module patches only names that are part of the package's surface, so the sam
 The committed fixture was recorded on the commit that folded the per-variant fp32 BatchNorm entry points into the general
 ones (bn_bwd_route families bn_fused / bn_sync / bn_seg).
 tests/test_conv_routes_host.py replays it in-process and compares with the committed fixture.
+
+The bf16 mode (sivae_hip.ops16: conv2d, conv2d_pool, conv2d_wgrad, bn_bwd) is recorded the same way, under its own switch
+variants (ops16.POOL_DGRAD, ops.BN_FUSED, SIVAE_DP_SAME_DEVICE, ops.SYNC_BN), into a second fixture:
+
+    python tests/conv_routes.py --bf16     # writes tests/golden/conv_routes_bf16.json.gz
+
+That fixture was recorded on the last commit whose ops16 launch functions still chose the entry point inline
+("pointcloud.hip: one definition per shared ReLU-BatchNorm/max expression"), before ops16 got route functions.
 """
 import contextlib
 import gzip
@@ -102,16 +110,31 @@ class _Mask:
         return 1 << 40
 
 
+class _MaskOf(_Mask):
+    """_Mask with the size of the meta tensor it stands for (ops16.bn_bwd checks it, and slices it per segment)"""
+
+    def __init__(self, t):
+        self.n = t.numel()
+
+    def numel(self):
+        return self.n
+
+    def __getitem__(self, sl):
+        return self
+
+
 def M(*shape, dtype=torch.float32):
     return torch.empty(shape, dtype=dtype, device="meta")
 
 
 @contextlib.contextmanager
-def recording(switches=None, same_device="0"):
-    """patch sivae_hip.ops as the module docstring says; yields (ops, events) — `events` is the list the recorder
-    appends to (clear it between cases)"""
-    from sivae_hip import ops
+def recording(switches=None, same_device="0", pool_dgrad=True):
+    """patch sivae_hip.ops as the module docstring says, and sivae_hip.ops16 likewise (it binds `_p` / `_s` at import and
+    has its own `_req16` and one switch, POOL_DGRAD); yields (ops, events) — `events` is the list the recorder appends
+    to (clear it between cases)"""
+    from sivae_hip import ops, ops16
     events = []
+    saved16 = {n: getattr(ops16, n) for n in ("_p", "_s", "_req16", "POOL_DGRAD")}
     names = list(SWITCHES) + ["_require", "_p", "_s", "workspace", "counters", "bn_fused_state", "TIMER"]
     saved = {n: getattr(ops, n) for n in names}
     saved_call = ops._lib.call
@@ -128,9 +151,12 @@ def recording(switches=None, same_device="0"):
         ops.bn_fused_state = lambda device: torch.empty(64, dtype=torch.int32, device="meta")
         ops.TIMER = _FakeTimer(events)
         ops._lib.call = lambda name, *args: events.append(["call", name] + [_enc(a) for a in args])
+        ops16._p, ops16._s, ops16._req16, ops16.POOL_DGRAD = ops._p, ops._s, ops._require, pool_dgrad
         yield ops, events
     finally:
         ops._lib.call = saved_call
+        for n, v in saved16.items():
+            setattr(ops16, n, v)
         for n, v in saved.items():
             setattr(ops, n, v)
         if saved_env is None:
@@ -191,8 +217,51 @@ def run_bn_dzsum(ops, B, C, H, W, nseg=1):
     return ops.bn_bwd_dzsum(torch.empty_like(x), torch.empty_like(x), x, M(nseg * C), M(nseg * C), M(C), nseg=nseg)
 
 
+# the bf16 mode (sivae_hip.ops16): blocked bf16 activations [B, C16/8, H, W, 8]; H, W are the OUTPUT map of a conv
+def X(B, C, H, W):
+    return M(B, ((C + 15) // 16) * 2, H, W, 8, dtype=torch.bfloat16)
+
+
+class _WP16:
+    """stands for a PackedW16 (the launches only take its buffer's address)"""
+    data = M(8, dtype=torch.bfloat16)
+
+
+def run_conv16(ops, B, Ci, Co, H, W, ks, bias=False, pro=False, upsample=False, want_stats=False, has_out=False,
+               accumulate=False, out_f32=False):
+    from sivae_hip import ops16
+    out = (M(B, Co, H, W) if out_f32 else X(B, Co, H, W)) if has_out else None
+    return ops16.conv2d(X(B, Ci, H // 2, W // 2) if upsample else X(B, Ci, H, W), _WP16, Ci, Co, ks,
+                        bias=M(Co) if bias else None, pro=_pro(Ci, 1) if pro else None, upsample=upsample,
+                        want_stats=want_stats, out=out, accumulate=accumulate, out_f32=out_f32)
+
+
+def run_pool16(ops, B, Ci, Co, H, W, has_out=False, accumulate=False):
+    from sivae_hip import ops16
+    return ops16.conv2d_pool(X(B, Ci, H, W), _WP16, Ci, Co, out=X(B, Co, H // 2, W // 2) if has_out else None,
+                             accumulate=accumulate)
+
+
+def run_wgrad16(ops, B, Ci, Co, H, W, ks, pro=False, upsample=False, has_out=False):
+    from sivae_hip import ops16
+    out = M(*((Co, Ci, 5, 1) if ks == ops16.KS51 else (Co, Ci, ks, ks))) if has_out else None
+    return ops16.conv2d_wgrad(X(B, Ci, H // 2, W // 2) if upsample else X(B, Ci, H, W), X(B, Co, H, W), Ci, Co, ks,
+                              pro=_pro(Ci, 1) if pro else None, upsample=upsample, out=out)
+
+
+def run_bn_bwd16(ops, B, C, H, W, y="saved", dy_pooled=False, want_dz=False, dz_sum=False, has_pg_out=False, nseg=1):
+    """y: the sign comes from the "saved" output, from the uint8 "mask", or ("none") is recomputed from x"""
+    from sivae_hip import ops16
+    x = X(B, C, H, W)
+    src = {"saved": torch.empty_like(x), "mask": _MaskOf(M(*x.shape[:4], dtype=torch.uint8)), "none": None}[y]
+    return ops16.bn_bwd(X(B, C, H // 2, W // 2) if dy_pooled else torch.empty_like(x), src, x, M(nseg * C), M(nseg * C),
+                        M(C), M(C), C, dy_pooled=dy_pooled, want_dz=want_dz, dz_sum=dz_sum,
+                        pg_out=(M(C), M(C)) if has_pg_out else None, nseg=nseg)
+
+
 RUNNERS = dict(fwd=run_fwd, wgrad=run_wgrad, up_dgrad=run_up_dgrad, dgrad_bnbwd=run_dgrad_bnbwd, bn_bwd=run_bn_bwd,
-               bn_signmask=run_bn_signmask, bn_dzsum=run_bn_dzsum)
+               bn_signmask=run_bn_signmask, bn_dzsum=run_bn_dzsum, conv16=run_conv16, pool16=run_pool16,
+               wgrad16=run_wgrad16, bn_bwd16=run_bn_bwd16)
 
 
 def _shapes(r):
@@ -424,6 +493,106 @@ def network_cases(ops, channels, image_size, B, nseg=1, cdim=3):
     return out
 
 
+# ---- the bf16 mode ---------------------------------------------------------------------------------------------------
+FIXTURE16 = os.path.join(os.path.dirname(FIXTURE), "conv_routes_bf16.json.gz")
+# (name, switch overrides of ops, SIVAE_DP_SAME_DEVICE, ops16.POOL_DGRAD): ops16 reads BN_FUSED and SYNC_BN of ops
+VARIANTS16 = [("default", {}, "0", True), ("ops16.POOL_DGRAD=0", {}, "0", False),
+              ("BN_FUSED=0", dict(BN_FUSED=False), "0", True), ("SIVAE_DP_SAME_DEVICE=1", {}, "1", True),
+              ("SYNC_BN", dict(SYNC_BN=_sync_stub), "0", True)]
+KS51 = 51  # (ops16.KS51: the 5-row x 1-column conv of the kw-packed RGB-side layers)
+
+
+def table_cases16(thin):
+    """[(kind, params)] of the bf16 table: one public call of ops16 each; thin: the table of the switch variants"""
+    out = []
+    batches = (16, 2) if thin else (128, 16, 2, 3)
+    pairs = [(24, 40), (128, 64), (512, 512)] if thin else [
+        (16, 16), (24, 40), (40, 24), (64, 64), (64, 128), (128, 64), (256, 256), (512, 512)]
+    maps = [(S, S) for S in MAPS] + [(6, 6), (7, 7), (12, 20), (8, 16)]
+    conv3 = [{}, dict(bias=True), dict(pro=True), dict(upsample=True), dict(want_stats=True),
+             dict(pro=True, want_stats=True), dict(upsample=True, want_stats=True), dict(has_out=True, accumulate=True),
+             dict(upsample=True, has_out=True, accumulate=True), dict(out_f32=True), dict(bias=True, out_f32=True),
+             dict(bias=True, want_stats=True)]
+    for B in batches:
+        for H, W in maps:
+            for Ci, Co in pairs:
+                if _skip(max(H, W), Ci, Co):
+                    continue
+                for fl in conv3:
+                    out.append(("conv16", dict(B=B, Ci=Ci, Co=Co, H=H, W=W, ks=3, **fl)))
+                for fl in ({}, dict(has_out=True, accumulate=True), dict(bias=True), dict(want_stats=True)):
+                    out.append(("conv16", dict(B=B, Ci=Ci, Co=Co, H=H, W=W, ks=1, **fl)))
+                for fl in ({}, dict(has_out=True, accumulate=True)):
+                    out.append(("pool16", dict(B=B, Ci=Ci, Co=Co, H=H, W=W, **fl)))
+                for fl in ({}, dict(pro=True), dict(upsample=True), dict(has_out=True)):
+                    out.append(("wgrad16", dict(B=B, Ci=Ci, Co=Co, H=H, W=W, ks=3, **fl)))
+                for fl in ({}, dict(has_out=True)):
+                    out.append(("wgrad16", dict(B=B, Ci=Ci, Co=Co, H=H, W=W, ks=1, **fl)))
+    # the RGB-side 5x5 layers, plain (1 / 3 / 4 image channels) and kw-packed (5 x 3 = 15 channels, 5 x 1 taps)
+    for B in batches:
+        for S in (32, 128, 256):
+            for ks, small in ((5, 1), (5, 3), (5, 4), (KS51, 15)):
+                for big in (16, 64, 128):
+                    for Ci, Co in ((small, big), (big, small)):
+                        for fl in ({}, dict(want_stats=True), dict(out_f32=True), dict(bias=True, out_f32=True)):
+                            out.append(("conv16", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=ks, **fl)))
+                        for fl in ({}, dict(has_out=True)):
+                            out.append(("wgrad16", dict(B=B, Ci=Ci, Co=Co, H=S, W=S, ks=ks, **fl)))
+    bn = [dict(y="mask", want_dz=True), dict(y="mask", want_dz=True, dz_sum=True),
+          dict(y="mask", dy_pooled=True, want_dz=True), dict(y="saved", want_dz=True), dict(y="saved", has_pg_out=True),
+          dict(y="none"), dict(y="none", dy_pooled=True), dict(y="none", has_pg_out=True)]
+    for B in batches:
+        for H, W in maps:
+            for C in (16, 24, 64, 512):
+                if _skip(max(H, W), C):
+                    continue
+                for nseg in (1, 2):
+                    if B % nseg == 0:
+                        for fl in bn:
+                            out.append(("bn_bwd16", dict(B=B, C=C, H=H, W=W, nseg=nseg, **fl)))
+    return out
+
+
+def production_cases16():
+    """[(case name, kind, params)]: the ops16 calls at every layer shape of the benchmarked bf16 networks
+    (block_checks16.PRODUCTION, unpaired and as segmented pairs) — block_checks16.walk_routes lists the convs whose
+    epilogue writes statistics (the stem's and both 3x3 convs of every block); each is recorded as a forward, as the data
+    gradient back through it (plain, and with the 2x2 block sum folded in), as its weight gradient and as the backward
+    of the BatchNorm that follows it"""
+    import block_checks16 as bc
+    out = []
+    for net, channels, size, B in bc.PRODUCTION:
+        for nseg in (1, 2):
+            convs, block_route = [], bc.block_route
+            bc.block_route = lambda *a, **k: None  # (only the shapes are wanted: this file records any commit's ops16)
+            try:
+                with contextlib.redirect_stdout(None):  # (the constructors print their shapes)
+                    bc.walk_routes(channels, size, B * nseg, nseg, convs=convs)
+            finally:
+                bc.block_route = block_route
+            for Ci, Co, H, W, ks in dict.fromkeys(convs):
+                d = dict(B=B * nseg, Ci=Ci, Co=Co, H=H, W=W)
+                cases = [("conv16", dict(d, ks=ks, want_stats=True)), ("conv16", dict(d, Ci=Co, Co=Ci, ks=ks)),
+                         ("wgrad16", dict(d, ks=ks, has_out=True))]
+                if ks == 3:
+                    cases.append(("pool16", dict(d, Ci=Co, Co=Ci)))
+                for fl in (dict(y="mask", want_dz=True), dict(y="mask", dy_pooled=True, want_dz=True, dz_sum=True),
+                           dict(y="none", has_pg_out=True)):
+                    cases.append(("bn_bwd16", dict(B=B * nseg, C=Co, H=H, W=W, nseg=nseg, **fl)))
+                out.extend(("%s nseg=%d: %s" % (net, nseg, case_name(k, p)), k, p) for k, p in cases)
+    return out
+
+
+def variant_cases16(vname):
+    seen, out = set(), []
+    for kind, p in table_cases16(thin=vname != "default"):
+        name = case_name(kind, p)
+        if name not in seen:
+            seen.add(name)
+            out.append((name, kind, p))
+    return out + production_cases16()
+
+
 # ---- recording -------------------------------------------------------------------------------------------------------
 def variant_cases(ops, vname):
     """[(case name, kind, params)] of one switch variant (call inside `recording` of that variant: the network walk asks
@@ -442,14 +611,14 @@ def variant_cases(ops, vname):
     return out
 
 
-def generate(on_case=None):
-    """-> {variant: [(case name, record)]}; on_case(ops, variant, name, kind, params, record) is called for every case
-    while the variant's switches are still set"""
+def generate(on_case=None, bf16=False):
+    """-> {variant: [(case name, record)]} of the fp32 dispatch, or (bf16) of the bf16 mode's; on_case(ops, variant, name,
+    kind, params, record) is called for every case while the variant's switches are still set"""
     out = {}
-    for vname, switches, same_device in VARIANTS:
-        with recording(switches, same_device) as (ops, events):
+    for vname, *settings in (VARIANTS16 if bf16 else VARIANTS):
+        with recording(*settings) as (ops, events):
             rows = []
-            for name, kind, p in variant_cases(ops, vname):
+            for name, kind, p in (variant_cases16(vname) if bf16 else variant_cases(ops, vname)):
                 rec = record_case(ops, events, kind, p)
                 rows.append((name, rec))
                 if on_case is not None:
@@ -489,8 +658,8 @@ def load_fixture(path=FIXTURE):
         return json.load(f)
 
 
-def write_fixture(path=FIXTURE):
-    data = json.dumps(compact(generate()), separators=(",", ":")).encode("utf-8")
+def write_fixture(path=FIXTURE, bf16=False):
+    data = json.dumps(compact(generate(bf16=bf16)), separators=(",", ":")).encode("utf-8")
     with open(path, "wb") as raw:
         with gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0, compresslevel=9) as f:
             f.write(data)
@@ -498,5 +667,7 @@ def write_fixture(path=FIXTURE):
 
 
 if __name__ == "__main__":
-    n, z = write_fixture(sys.argv[1] if len(sys.argv) > 1 else FIXTURE)
-    print("wrote %s: %d bytes of JSON, %d compressed" % (sys.argv[1] if len(sys.argv) > 1 else FIXTURE, n, z))
+    args = [a for a in sys.argv[1:] if a != "--bf16"]
+    path = args[0] if args else (FIXTURE16 if "--bf16" in sys.argv else FIXTURE)
+    n, z = write_fixture(path, bf16="--bf16" in sys.argv)
+    print("wrote %s: %d bytes of JSON, %d compressed" % (path, n, z))

@@ -1,4 +1,6 @@
-"""Host-only checks that tie the bf16 mode's dispatch to its tests (library predicates only: no GPU needed).
+"""Host-only checks that tie the bf16 mode's dispatch to its tests (library predicates only: no GPU needed).  The route
+classes come from the route functions of sivae_hip.ops16 (conv2d_route, bn_bwd_route, the block plan's pooled data
+gradient) — the code that launches —, which tests/test_conv_routes_host.py holds to a recording of the dispatch.
 
 * every route class a block / stem / predict call of the benchmarked bf16 iterations takes (pixel tile or split-K plan
   of both 3x3 convs, pooled data gradient, one-launch BatchNorm backward, expansion conv, upsampled input, fused
@@ -14,8 +16,8 @@ import block_checks16 as bc
 def test_every_benchmarked_bf16_route_has_a_block_referee():
     """walks nn._run_main over the Encoder / Decoder of config 3 (128x128, batch 128), celeb256_bf16_bs128 and the
     16-image 256x256 shard, unpaired and as segmented pairs, and requires each route class to be the class of a
-    block_checks16 case at that case's own (smaller) batch — the classes are computed from the library's predicates
-    in both places, so a dispatch change that opens a new route fails here until a case covers it"""
+    block_checks16 case at that case's own (smaller) batch — the classes are asked of ops16's route functions in both
+    places, so a dispatch change that opens a new route fails here until a case covers it"""
     prod = bc.production_routes()
     assert len(prod) >= 20, len(prod)  # (sanity: the walk saw the networks)
     cov = bc.covered_routes()
@@ -58,9 +60,8 @@ def _nets():
 @pytest.mark.parametrize("size,channels", _nets(), ids=lambda v: str(v))
 def test_bf16_segments_supported_never_mixes_two_passes(size, channels):
     """Wherever nn.segments_supported(size, seg_images, "bf16") admits a pair (nseg = 2), every conv whose epilogue
-    writes BatchNorm statistics — at 2 * seg_images images, the statistics rows the library will lay out for it
-    (sivae_bf16_conv2d_splitk_stats_rows: one row per image for a split-K plan, else sivae_bf16_conv2d_num_px_tiles) —
-    must be cut into the two passes without a row holding images of both (the rule ops.bn_stats_from_conv enforces,
+    writes BatchNorm statistics — at 2 * seg_images images, the statistics rows of its route (ops16.conv2d_route: one
+    row per image for a split-K plan, else one per pixel tile) — must be cut into the two passes without a row holding images of both (the rule ops.bn_stats_from_conv enforces,
     ops.stats_rows_fit_segments).
 
     The predicate's hard-coded `seg_images % 16 == 0` holds because of a bound in bf16_conv.hip px_tile_3x3: a tile
@@ -68,9 +69,8 @@ def test_bf16_segments_supported_never_mixes_two_passes(size, channels):
     images x (TH + 2) x (TW + 2)) — which keeps every tile of the 4 x 4 maps (the smallest map of these nets) at <= 16
     images (the 64-channel big tile there would hold 32 images with a 1152-element plane).  Tiles of the 8 x 8 / 16 x 16
     maps hold fewer; the stem's 5x5 tiles stay inside one image.  A tile change that breaks that bound fails here."""
-    from sivae_hip import lib, ops
+    from sivae_hip import ops, ops16
     from sivae_hip import nn as N
-    L = lib.load()
     convs = []
     bc.walk_routes(channels, size, 2, nseg=1, convs=convs)
     shapes = sorted(set(convs))
@@ -81,8 +81,7 @@ def test_bf16_segments_supported_never_mixes_two_passes(size, channels):
         admitted += 1
         B = 2 * seg
         for Ci, Co, H, W, ks in shapes:
-            rows = (L.sivae_bf16_conv2d_splitk_stats_rows(B, Ci, Co, H, W, ks) if ks == 3
-                    else L.sivae_bf16_conv2d_num_px_tiles(B, Co, H, W, ks))
+            rows = ops16.conv2d_route(B, Ci, Co, H, W, ks, want_stats=True).stats_rows
             assert rows > 0, (Ci, Co, H, W, ks, rows)
             assert ops.stats_rows_fit_segments(rows, B, 2), \
                 "segments_supported(%d, %d, 'bf16') but conv %s has %d statistics rows at %d images" % (

@@ -1,4 +1,4 @@
-"""Host-only checks of the fp32 mode's dispatch (library predicates only: no GPU needed).
+"""Host-only checks of the dispatch of both modes (library predicates only: no GPU needed).
 
 tests/conv_routes.py drives the public launch functions of sivae_hip.ops on meta tensors with the C-ABI call replaced by
 a recorder.  tests/golden/conv_routes_fp32.json.gz is what it recorded (`python tests/conv_routes.py`) on the commit that
@@ -11,6 +11,13 @@ kernel pull request that changes a route regenerates it from the commit that int
 (b) for every case, the route function names what the launch then does: entry point, timer key, executed FLOPs,
     statistics rows, the materialised input, the refusal;
 (c) pinned statements about the headline network (celeb256, channels 64-128-256-512-512-512).
+
+The bf16 mode (sivae_hip.ops16) has the same two checks on tests/golden/conv_routes_bf16.json.gz
+(`python tests/conv_routes.py --bf16`), recorded on the last commit whose ops16 launch functions still chose the entry
+point inline ("pointcloud.hip: one definition per shared ReLU-BatchNorm/max expression"); its switch variants include
+synchronised BatchNorm and two ranks on one device.  In (b) the workspace size is compared too, and the pooled data
+gradient's route — which conv2d_pool never consults to refuse — must be refused exactly where the switch is off, the
+map is odd or conv2d launches the split-K entry for the same layer.
 """
 import pytest
 
@@ -31,6 +38,15 @@ def _route(ops, kind, p):
         return ops.bn_bwd_route(p["B"], p["C"], p["H"], p["W"], op=kind[3:] if kind != "bn_bwd" else kind,
                                 four_d=not p.get("flat", False), dy_pooled=p.get("dy_pooled", False),
                                 nseg=p.get("nseg", 1))
+    if kind.endswith("16"):
+        from sivae_hip import ops16
+        fn = dict(conv16=ops16.conv2d_route, pool16=ops16.conv2d_pool_route, wgrad16=ops16.conv2d_wgrad_route)
+        if kind == "bn_bwd16":
+            return ops16.bn_bwd_route(p["B"], p["C"], p["H"], p["W"], nseg=p["nseg"])
+        # (an upsampled input of an odd map: the output map is twice the input's, one less than the case names)
+        H, W = (p["H"] // 2 * 2, p["W"] // 2 * 2) if p.get("upsample") else (p["H"], p["W"])
+        return fn[kind](p["B"], p["Ci"], p["Co"], H, W, *([p["ks"]] if "ks" in p else []), **{
+            k: v for k, v in p.items() if k in ("bias", "out_f32", "want_stats") and kind == "conv16"})
     return None
 
 
@@ -59,6 +75,36 @@ def _route_vs_record(r, p, rec):
     return None
 
 
+def _route16_vs_record(ops, events, r, kind, p, rec):
+    """_route_vs_record for a bf16 case, plus the workspace size and the planner's refusal of the pooled data gradient"""
+    if kind == "pool16":
+        twin = cr.record_case(ops, events, "conv16", dict(B=p["B"], Ci=p["Ci"], Co=p["Co"], H=p["H"], W=p["W"], ks=3))
+        from sivae_hip import ops16
+        refused = not ops16.POOL_DGRAD or p["H"] % 2 or p["W"] % 2 or twin[0][1] == "sivae_bf16_conv2d_fwd_splitk"
+        if (r.error is not None) != bool(refused):
+            return "pooled data gradient refused: route %s, expected %s" % (r.error, bool(refused))
+        r = r._replace(error=None)
+    msg = _route_vs_record(r, p, rec)
+    launch = [ev for ev in rec if ev[0] == "call"][0]
+    if msg is None and r.ws_bytes and launch[-2] != r.ws_bytes:  # (entries with a workspace end: ..., its size, stream)
+        msg = "workspace of %d bytes, route says %d" % (launch[-2], r.ws_bytes)
+    return msg
+
+
+@pytest.fixture(scope="module")
+def replay16():
+    """one run of the bf16 generator on this tree: ({variant: [(case name, record)]}, route disagreements)"""
+    wrong = []
+
+    def on_case(ops, variant, name, kind, p, rec):
+        events = ops.TIMER.events
+        msg = _route16_vs_record(ops, events, _route(ops, kind, p), kind, p, rec)
+        if msg is not None:
+            wrong.append("[%s] %s: %s" % (variant, name, msg))
+
+    return cr.generate(on_case, bf16=True), wrong
+
+
 @pytest.fixture(scope="module")
 def replay():
     """one run of the generator on this tree: ({variant: [(case name, record)]}, route disagreements, the cases of the
@@ -77,9 +123,7 @@ def replay():
     return cr.generate(on_case), wrong, headline
 
 
-def test_replay_equals_the_recording_of_the_previous_dispatch(replay):
-    want = cr.expand(cr.load_fixture())
-    got = replay[0]
+def _same_as_fixture(got, want, floor):
     assert list(got) == list(want), "switch variants differ: %s vs %s" % (list(got), list(want))
     n = 0
     for variant, rows in want.items():
@@ -88,7 +132,20 @@ def test_replay_equals_the_recording_of_the_previous_dispatch(replay):
         for (name, a), (_, b) in zip(rows, new):
             assert a == b, "[%s] %s\n  recorded: %s\n  now:      %s" % (variant, name, a, b)
             n += 1
-    assert n >= 100000, n  # (sanity: the table and the network walks were there)
+    assert n >= floor, n  # (sanity: the table and the network walks were there)
+
+
+def test_replay_equals_the_recording_of_the_previous_dispatch(replay):
+    _same_as_fixture(replay[0], cr.expand(cr.load_fixture()), 100000)
+
+
+def test_bf16_replay_equals_the_recording_of_the_previous_dispatch(replay16):
+    _same_as_fixture(replay16[0], cr.expand(cr.load_fixture(cr.FIXTURE16)), 30398)  # (the recorded count)
+
+
+def test_the_bf16_route_is_what_is_launched(replay16):
+    wrong = replay16[1]
+    assert not wrong, "%d cases; first: %s" % (len(wrong), wrong[0])
 
 
 def test_the_route_is_what_is_launched(replay):
