@@ -725,7 +725,7 @@ int sivae_voxel_histogram(const float* pc, long long stride_s, long long stride_
 int sivae_js_divergence(const void* P, const void* Q, int p_is_f64, int q_is_f64, int n, double* out,
                         sivae_stream_t stream);
 
-/* ---- point clouds: minimum matching distance and coverage (pc_eval.hip) -------------------------------------------
+/* ---- point clouds: minimum matching distance, coverage and 1-NN accuracy (pc_eval.hip) -----------------------------
  * What soft_intro_vae_3d/README.md:47-48 asks for after evaluation/generate_data_for_metrics.py has saved its arrays: the
  * all-pairs Chamfer matrix of two sets of clouds.  sample: S clouds of M points, ref: R clouds of N points, each read in
  * place through three ELEMENT strides (cloud, point, coordinate) as sivae_occupancy_grid reads its clouds.  With
@@ -748,6 +748,35 @@ int sivae_chamfer_matrix(const float* sample, long long sample_stride_s, long lo
  * (+inf, 0).  SIVAE_ERR_RANGE for S R >= 2^31 - 1. */
 int sivae_match_min(const float* D, int S, int R, float* row_min, int* row_arg, float* col_min, int* col_arg,
                     sivae_stream_t stream);
+/* 1-nearest-neighbour accuracy, the third figure people report beside MMD and COV in the evaluation that
+ * soft_intro_vae_3d/README.md:47-48 sends the arrays of evaluation/generate_data_for_metrics.py to: a leave-one-out test
+ * over the union of the two sets, which needs each set's matrix against ITSELF.
+ * sivae_chamfer_matrix_self: D [S][S] float32 for ONE set of S clouds of M points (three element strides as above).  For
+ * i <= j, D[i][j] is bit for bit the entry sivae_chamfer_matrix computes for (sample = ref = clouds): same flags, same
+ * arithmetic, same fixed summation order, the diagonal included and computed (exactly 0 for finite clouds); D[j][i] is a
+ * copy of D[i][j] (for M = N that arithmetic is symmetric in its two clouds bit for bit, so the whole matrix equals the
+ * full one's).  A cloud with a non-finite coordinate makes its row and its column non-finite.  Only the pairs i <= j are
+ * computed, enumerated by FOLDED rows: folded row f in [0, ceil(S / 2)) has the S + 1 columns c; c < S - f is the pair
+ * (f, f + c), any other c the pair (S - 1 - f, S - 1 - f + c - (S - f)); for odd S the middle row (S - 1 - f == f) has only
+ * its first S - f columns.  One call computes the folded rows f0 <= f < f1 (the caller bounds a launch with the range) and
+ * stores both D[i][j] and D[j][i] of each pair.  SIVAE_ERR_SHAPE for non-positive sizes or a range outside
+ * 0 <= f0 < f1 <= ceil(S / 2); SIVAE_ERR_RANGE for S S >= 2^31 - 1; SIVAE_ERR_MODE for a flag that is not 0 or 1.  The
+ * workspace (sized for f1 - f0 folded rows: M words per launched block) is only used when M > 2048; its size is 0
+ * otherwise, the pointer must still not be NULL (SIVAE_ERR_WORKSPACE). */
+size_t sivae_chamfer_matrix_self_workspace_bytes(int frows, int S, int M);
+int sivae_chamfer_matrix_self(const float* clouds, long long stride_s, long long stride_n, long long stride_c, float* D,
+                              int S, int M, int f0, int f1, int normalize, int use_sqrt, void* workspace,
+                              size_t workspace_bytes, sivae_stream_t stream);
+/* The joint leave-one-out nearest neighbour behind 1-NN accuracy (same citation).  Dss [S][S], Dsr [S][R], Drr [R][R]:
+ * contiguous float32.  The T = S + R items are the samples 0 .. S - 1 and the references S .. T - 1; the distance from
+ * item t to item u != t is read from ROW t of the joint matrix [[Dss, Dsr], [Dsr^T, Drr]]:
+ *   t < S, u < S: Dss[t][u];   t < S, u >= S: Dsr[t][u - S];   t >= S, u < S: Dsr[u][t - S];   t >= S, u >= S: Drr[t - S][u - S]
+ * (for a Dss or Drr that is not symmetric, this row rule is the definition).  The entry u = t is never a candidate,
+ * whatever it holds.  nn_arg[t] (int32 [T]) is the u of the smallest distance, the lowest u on a tie, nn_val[t] (float32
+ * [T]) that distance; +inf and NaN never win; an item with no candidate left gives (+inf, -1).  No atomics, no workspace:
+ * two runs are bit-identical.  SIVAE_ERR_RANGE for (S + R)(S + R) >= 2^31 - 1. */
+int sivae_nn1_loo(const float* Dss, const float* Dsr, const float* Drr, int S, int R, float* nn_val, int* nn_arg,
+                  sivae_stream_t stream);
 
 /* ---- point clouds: the earth mover's distance matrix (pc_emd.hip) --------------------------------------------------
  * MMD-EMD / COV-EMD, the two remaining figures of the tables soft_intro_vae_3d/README.md:47-48 points to (the notebook's

@@ -21,6 +21,8 @@ csrc/pc_eval.hip, not differentiable:
   chamfer_matrix(sample [S, M, 3], ref [R, N, 3], normalize=True, use_sqrt=False) -> D [S, R], D[s, r] = CD(sample_s, ref_r)
   match_min(D [S, R])                                        -> (row_min [S], row_arg int32 [S], col_min [R], col_arg int32 [R])
   emd_matrix(sample [S, M, 3], ref [R, N, 3], normalize=True) -> D [S, R], D[s, r] = EMD(left = ref_r, right = sample_s)  (csrc/pc_emd.hip)
+  chamfer_matrix_self(clouds [S, M, 3], normalize=True, use_sqrt=False) -> J [S, S] = chamfer_matrix(clouds, clouds), upper triangle computed, mirrored
+  nn1_loo(Dss [S, S], Dsr [S, R], Drr [R, R])                -> (nn_val [S + R], nn_arg int32 [S + R]): 1-NN accuracy's leave-one-out neighbour
 
 The pointwise convolutions and the MLPs run on what exists (`ops.conv2d_fwd` / `conv2d_wgrad` with ks = 1, `SF.linear`).
 There is no CPU path: a CPU tensor raises the engine's usual message.
@@ -375,6 +377,61 @@ def match_min(D):
     if t0 is not None:
         timer_end(t0, "match_min_kernel", 4.0 * S * R)
     return row_min, row_arg, col_min, col_arg
+
+
+# ------------------------------------------------------------------------------------------------ 1-NN accuracy
+def chamfer_matrix_self(clouds, normalize=True, use_sqrt=False):
+    """The Chamfer matrix of ONE set against itself, clouds [S, M, 3] (float32, any strides) -> J [S, S] float32: the upper
+    triangle with the diagonal is bit for bit that of chamfer_matrix(clouds, clouds) (the diagonal exactly 0 for finite
+    clouds), J[j, i] is a copy of J[i, j].  Only the S (S + 1) / 2 pairs i <= j are computed, walked by folded rows (row f
+    of the triangle followed by row S - 1 - f: S + 1 pairs each) in slabs of MATRIX_POINT_PAIRS_PER_LAUNCH point pairs.  A
+    cloud with a non-finite coordinate makes its row and column non-finite."""
+    if clouds.dim() != 3 or clouds.shape[2] != 3:  # (the shape error before the device's, as chamfer_matrix does)
+        raise ValueError("sivae_hip.chamfer_matrix_self: expected point clouds [S, N, 3], got %s" % (tuple(clouds.shape),))
+    S, M, st = _require_clouds(clouds, "chamfer_matrix_self")
+    if S * S >= 0x7fffffff:
+        raise ValueError("sivae_hip.chamfer_matrix_self: %d x %d cloud pairs do not fit an int32 index" % (S, S))
+    J = torch.empty((S, S), dtype=torch.float32, device=clouds.device)
+    folded = (S + 1) // 2
+    slab = max(1, min(folded, MATRIX_POINT_PAIRS_PER_LAUNCH // ((S + 1) * M * M)))
+    ws = workspace(_lib.load().sivae_chamfer_matrix_self_workspace_bytes(slab, S, M), clouds.device)
+    for f0 in range(0, folded, slab):
+        f1 = min(folded, f0 + slab)
+        t0 = timer_begin()
+        _lib.call("sivae_chamfer_matrix_self", _p(clouds), st[0], st[1], st[2], _p(J), S, M, f0, f1, int(bool(normalize)),
+                  int(bool(use_sqrt)), _p(ws), ws.numel(), _s(clouds))
+        if t0 is not None:
+            # 8 per point pair computed, as chamfer_matrix counts; the middle folded row f of an odd S has S - f pairs
+            pairs = (f1 - f0) * (S + 1) - (f1 if S % 2 and f1 == folded else 0)
+            timer_end(t0, "chamfer_matrix_self_kernel", 8.0 * pairs * M * M)
+    return J
+
+
+def nn1_loo(Dss, Dsr, Drr):
+    """The joint leave-one-out nearest neighbour behind 1-NN accuracy: Dss [S, S], Dsr [S, R], Drr [R, R] (float32,
+    contiguous) -> (nn_val float32 [S + R], nn_arg int32 [S + R]).  Items 0 .. S - 1 are the samples, S .. S + R - 1 the
+    references; item t's distances are row t of [[Dss, Dsr], [Dsr^T, Drr]] without the entry t itself.  The lowest index
+    wins a tie, +inf / NaN entries never win, an item with no candidate left gives (+inf, -1)."""
+    for name, D in (("Dss", Dss), ("Dsr", Dsr), ("Drr", Drr)):
+        if D.dim() != 2 or D.shape[0] == 0 or D.shape[1] == 0:
+            raise ValueError("sivae_hip.nn1_loo: %s: expected a matrix, got %s" % (name, tuple(D.shape)))
+    S, R = Dsr.shape
+    if tuple(Dss.shape) != (S, S) or tuple(Drr.shape) != (R, R):
+        raise ValueError("sivae_hip.nn1_loo: expected Dss [S, S], Dsr [S, R], Drr [R, R], got %s, %s, %s"
+                         % (tuple(Dss.shape), tuple(Dsr.shape), tuple(Drr.shape)))
+    _require_f32(Dss, Dsr, Drr)
+    if Dss.device != Dsr.device or Drr.device != Dsr.device:
+        raise ValueError("sivae_hip.nn1_loo: the matrices are on %s, %s and %s" % (Dss.device, Dsr.device, Drr.device))
+    T = S + R
+    if T * T >= 0x7fffffff:
+        raise ValueError("sivae_hip.nn1_loo: %d x %d item pairs do not fit an int32 index" % (T, T))
+    nn_val = torch.empty(T, dtype=torch.float32, device=Dsr.device)
+    nn_arg = torch.empty(T, dtype=torch.int32, device=Dsr.device)
+    t0 = timer_begin()
+    _lib.call("sivae_nn1_loo", _p(Dss), _p(Dsr), _p(Drr), S, R, _p(nn_val), _p(nn_arg), _s(Dsr))
+    if t0 is not None:
+        timer_end(t0, "nn1_loo_kernel", 2.0 * T * T)
+    return nn_val, nn_arg
 
 
 # ------------------------------------------------------------------------------------------------ MMD-EMD / COV-EMD

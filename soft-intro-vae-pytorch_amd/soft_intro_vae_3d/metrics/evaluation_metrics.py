@@ -22,7 +22,8 @@ if _PKG not in sys.path:
     sys.path.append(_PKG)
 from sivae_hip import pointcloud as PC  # noqa: E402
 
-__all__ = ['chamfer_matrix', 'emd_matrix', 'minimum_mathing_distance', 'minimum_matching_distance', 'coverage']
+__all__ = ['chamfer_matrix', 'emd_matrix', 'minimum_mathing_distance', 'minimum_matching_distance', 'coverage',
+           'chamfer_matrix_self', 'one_nn_accuracy']
 
 
 def _device_of(*arrays):
@@ -66,6 +67,32 @@ def emd_matrix(sample_pcs, ref_pcs, normalize=True):
     return PC.emd_matrix(_clouds(sample_pcs, dev, "sample_pcs"), _clouds(ref_pcs, dev, "ref_pcs"), normalize)
 
 
+def chamfer_matrix_self(pcs, normalize=True, use_sqrt=False):
+    """J [S, S] float32 on the device, the Chamfer matrix of one set against itself: chamfer_matrix(pcs, pcs) at half the
+    work (the pairs i <= j are computed, bit for bit its entries, and mirrored)"""
+    if np.ndim(pcs) != 3 or np.shape(pcs)[2] != 3:  # (the shape error before any device is asked for)
+        raise ValueError("pcs: expected point clouds [S, N, 3], got %s" % (tuple(np.shape(pcs)),))
+    return PC.chamfer_matrix_self(_clouds(pcs, _device_of(pcs), "pcs"), normalize, use_sqrt)
+
+
+def _given_matrix(dist, name, device_of):
+    """a caller's matrix -> float32, contiguous, on the device (`device_of()` names it when `dist` is host data)"""
+    if not isinstance(dist, torch.Tensor):
+        dist = torch.from_numpy(np.ascontiguousarray(dist, dtype=np.float32))
+    if dist.dim() != 2:
+        raise ValueError("%s: expected a matrix [S, R], got %s" % (name, tuple(dist.shape)))
+    if not dist.is_cuda:
+        dist = dist.to(device_of())
+    return dist.float().contiguous()
+
+
+def _finite(dist):
+    if not bool(torch.isfinite(dist).all()):
+        raise ValueError("the distance matrix has %d non-finite entries (a cloud with a NaN or infinite coordinate?)"
+                         % int((~torch.isfinite(dist)).sum()))
+    return dist
+
+
 def _matrix(sample_pcs, ref_pcs, normalize, use_sqrt, use_EMD, dist):
     if use_EMD:
         raise NotImplementedError("use_EMD is not wired to the earth mover's matrix: pass dist=emd_matrix(sample_pcs, "
@@ -73,17 +100,8 @@ def _matrix(sample_pcs, ref_pcs, normalize, use_sqrt, use_EMD, dist):
     if dist is None:
         dist = chamfer_matrix(sample_pcs, ref_pcs, normalize, use_sqrt)
     else:
-        if not isinstance(dist, torch.Tensor):
-            dist = torch.from_numpy(np.ascontiguousarray(dist, dtype=np.float32))
-        if dist.dim() != 2:
-            raise ValueError("dist: expected a matrix [S, R], got %s" % (tuple(dist.shape),))
-        if not dist.is_cuda:
-            dist = dist.to(_device_of(sample_pcs, ref_pcs))
-        dist = dist.float().contiguous()
-    if not bool(torch.isfinite(dist).all()):
-        raise ValueError("the distance matrix has %d non-finite entries (a cloud with a NaN or infinite coordinate?)"
-                         % int((~torch.isfinite(dist)).sum()))
-    return dist
+        dist = _given_matrix(dist, "dist", lambda: _device_of(sample_pcs, ref_pcs))
+    return _finite(dist)
 
 
 def minimum_mathing_distance(sample_pcs, ref_pcs, batch_size=None, normalize=True, sess=None, verbose=False, use_sqrt=False,
@@ -111,3 +129,46 @@ def coverage(sample_pcs, ref_pcs, batch_size=None, normalize=True, sess=None, ve
     if ret_dist:
         return cov, matched_ref, row_min.cpu().numpy()
     return cov, matched_ref
+
+
+def one_nn_accuracy(sample_pcs, ref_pcs, normalize=True, use_sqrt=False, metric="cd", dist=None, dist_ss=None,
+                    dist_rr=None):
+    """1-nearest-neighbour accuracy (1-NNA): every cloud of the union of the two sets is assigned the set of its nearest
+    OTHER cloud; the score is the fraction assigned to their own set (0.5: the sets cannot be told apart, 1.0: trivially
+    separable).  -> dict(acc, acc_sample, acc_ref: floats; nn: int64 numpy [S + R], the neighbour's joint index (samples
+    0 .. S - 1, references S .. S + R - 1, the lowest on a tie); nn_dist: float32 numpy [S + R]).
+    metric "cd": Chamfer matrices (`chamfer_matrix_self` for each set, `chamfer_matrix` across); "emd": `emd_matrix` for all
+    three (whole matrices: the approximate matching is not symmetric; item t reads ITS row).  `dist` [S, R] is the matrix
+    `minimum_mathing_distance` and `coverage` take, `dist_ss` [S, S] and `dist_rr` [R, R] the same-set ones; the flags of
+    a given matrix are its own."""
+    if metric not in ("cd", "emd"):
+        raise ValueError("metric: expected 'cd' or 'emd', got %r" % (metric,))
+
+    def device():
+        return _device_of(sample_pcs, ref_pcs, dist, dist_ss, dist_rr)
+
+    need = [("sample_pcs", sample_pcs, dist is None or dist_ss is None), ("ref_pcs", ref_pcs, dist is None or dist_rr is None)]
+    for name, pcs, needed in need:  # (the shape error before any device is asked for)
+        if needed and (np.ndim(pcs) != 3 or np.shape(pcs)[2] != 3):
+            raise ValueError("%s: expected point clouds [S, N, 3], got %s" % (name, tuple(np.shape(pcs))))
+    # (host clouds are uploaded once, not once per matrix)
+    sample_pcs, ref_pcs = (_clouds(pcs, device(), name) if needed else pcs for name, pcs, needed in need)
+
+    def build(name):
+        if name == "dist":
+            return (emd_matrix(sample_pcs, ref_pcs, normalize) if metric == "emd"
+                    else chamfer_matrix(sample_pcs, ref_pcs, normalize, use_sqrt))
+        pcs = sample_pcs if name == "dist_ss" else ref_pcs
+        return emd_matrix(pcs, pcs, normalize) if metric == "emd" else chamfer_matrix_self(pcs, normalize, use_sqrt)
+
+    Dss, Dsr, Drr = (_finite(build(name) if given is None else _given_matrix(given, name, device))
+                     for name, given in (("dist_ss", dist_ss), ("dist", dist), ("dist_rr", dist_rr)))
+    S, R = Dsr.shape
+    if tuple(Dss.shape) != (S, S) or tuple(Drr.shape) != (R, R):
+        raise ValueError("expected dist_ss [S, S], dist [S, R] and dist_rr [R, R], got %s, %s and %s"
+                         % (tuple(Dss.shape), tuple(Dsr.shape), tuple(Drr.shape)))
+    nn_val, nn_arg = PC.nn1_loo(Dss, Dsr, Drr)
+    nn = nn_arg.cpu().numpy().astype(np.int64)
+    own = (nn < S) == (np.arange(S + R) < S)
+    return dict(acc=float(np.mean(own, dtype=np.float64)), acc_sample=float(np.mean(own[:S], dtype=np.float64)),
+                acc_ref=float(np.mean(own[S:], dtype=np.float64)), nn=nn, nn_dist=nn_val.cpu().numpy())

@@ -13,11 +13,18 @@ that fails):
   full   the whole 2400 x 800 matrix ONCE with the new op only, each launch timed (the longest single launch is what
          pointcloud.MATRIX_POINT_PAIRS_PER_LAUNCH bounds), then match_min.
 
+  self   1-NN accuracy's matrices, run on its own (the driver does not start it): 240 clouds of 2048 points,
+         `chamfer_matrix(x, x)` against `chamfer_matrix_self(x)` (the pairs i <= j by folded rows, mirrored), one warm-up
+         call of each, then 5 rounds alternating; the two results must be equal bit for bit.  Also: the longest single
+         launch of the self form, and `nn1_loo` on random matrices at S = 2400, R = 800.  Its raw line goes to
+         profiles/pc_eval_self_bench.txt.
+
 Each step prints one JSON line; the driver appends the raw lines to profiles/pc_eval_bench.txt.
 
-    python tools/bench_pc_eval.py [--out profiles/pc_eval_bench.txt]        # the driver: both steps
+    python tools/bench_pc_eval.py [--out profiles/pc_eval_bench.txt]        # the driver: ab and full
     python tools/bench_pc_eval.py --step ab [--sample 240] [--ref 800] [--points 2048] [--rounds 5]
     python tools/bench_pc_eval.py --step full [--sample 2400] [--ref 800] [--points 2048]
+    python tools/bench_pc_eval.py --step self [--sample 240] [--points 2048] [--rounds 5] [--out profiles/pc_eval_self_bench.txt]
 """
 import argparse
 import json
@@ -30,7 +37,7 @@ PKG = os.path.join(REPO, "soft-intro-vae-pytorch_amd")
 if PKG not in sys.path:
     sys.path.insert(0, PKG)
 
-STEP_TIMEOUT_S = {"ab": 240, "full": 180}
+STEP_TIMEOUT_S = {"ab": 240, "full": 180}  # (the driver's steps)
 
 
 def _stats(ms):
@@ -137,6 +144,63 @@ def step_full(a):
     print(json.dumps(res))
 
 
+def step_self(a):
+    import torch
+    from sivae_hip import pointcloud as PC
+    S = a.sample if a.sample else 240
+    x = _inputs(torch, a, S)[0]
+    M = a.points
+    launches = []
+    real = PC._lib.call
+
+    def call(name, *args):
+        if name != "sivae_chamfer_matrix_self":
+            return real(name, *args)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        rc = real(name, *args)
+        e1.record()
+        launches.append((e0, e1))
+        return rc
+
+    def full():
+        return PC.chamfer_matrix(x, x, normalize=False)
+
+    def self_():
+        return PC.chamfer_matrix_self(x, normalize=False)
+
+    D0, D1 = full(), self_()  # (warm-up)
+    torch.cuda.synchronize()
+    ms = dict(full=[], self=[])
+    PC._lib.call = call
+    try:
+        for _ in range(a.rounds):
+            for name, fn in (("full", full), ("self", self_)):
+                ms[name].append(_timed(torch, fn)[1])
+    finally:
+        PC._lib.call = real
+    per_launch = [e0.elapsed_time(e1) for e0, e1 in launches]
+    # nn1_loo at the protocol's sizes, on random matrices (it reads (S + R)^2 words once)
+    g = torch.Generator().manual_seed(1)
+    Sn, Rn = 2400, a.ref
+    Dss, Dsr, Drr = (torch.rand(r, c, generator=g).to(x.device) for r, c in ((Sn, Sn), (Sn, Rn), (Rn, Rn)))
+    nn = [_timed(torch, lambda: PC.nn1_loo(Dss, Dsr, Drr))[1] for _ in range(a.rounds + 1)][1:]
+    res = dict(step="self", clouds=S, points=M, rounds=a.rounds, clock_mhz=a.clock_mhz, **_device(torch))
+    res["full"], res["self"], res["nn1_loo"] = _stats(ms["full"]), _stats(ms["self"]), _stats(nn)
+    res["nn1_loo_sizes"] = [Sn, Rn]
+    res["equal_bit_for_bit"] = bool(torch.equal(D0, D1))
+    res["ratio_of_medians"] = round(res["self"]["median_ms"] / res["full"]["median_ms"], 4)
+    res["ratio_by_pair_count"] = round((S + 1) / (2.0 * S), 4)
+    res["launches_per_call"] = len(per_launch) // a.rounds
+    res["longest_launch_ms"] = round(max(per_launch), 3)
+    res["point_pairs_per_launch"] = PC.MATRIX_POINT_PAIRS_PER_LAUNCH
+    _rates(res, S, (S + 1) / 2.0, M, M, res["self"]["median_ms"], res["compute_units"])
+    print(json.dumps(res))
+    out = a.out if os.path.isabs(a.out) else os.path.join(REPO, a.out)
+    with open(out, "a") as f:
+        f.write(json.dumps(res) + "\n")
+
+
 def drive(a):
     out = a.out if os.path.isabs(a.out) else os.path.join(REPO, a.out)
     for step in ("ab", "full"):
@@ -152,20 +216,22 @@ def drive(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=("ab", "full"))
+    ap.add_argument("--step", choices=("ab", "full", "self"))
     ap.add_argument("--sample", type=int, default=0, help="sample clouds (default: 240 for ab, 2400 for full)")
     ap.add_argument("--ref", type=int, default=800)
     ap.add_argument("--points", type=int, default=2048)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--clock-mhz", type=float, default=2400.0, help="engine clock the VALU issue rate is quoted at")
-    ap.add_argument("--out", default=os.path.join("profiles", "pc_eval_bench.txt"))
+    ap.add_argument("--out", default=None, help="raw lines: profiles/pc_eval_bench.txt, pc_eval_self_bench.txt for --step self")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "pc_eval_self_bench.txt" if a.step == "self" else "pc_eval_bench.txt")
     if a.step is None:
         return drive(a)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_pc_eval: needs a ROCm device (timings on a CPU would say nothing)")
-    (step_ab if a.step == "ab" else step_full)(a)
+    dict(ab=step_ab, full=step_full, self=step_self)[a.step](a)
 
 
 if __name__ == "__main__":
