@@ -807,6 +807,32 @@ int sivae_emd_matrix(const float* sample, long long sample_stride_s, long long s
                      int S, int R, int M, int N, int s0, int s1, int normalize, void* workspace, size_t workspace_bytes,
                      sivae_stream_t stream);
 
+/* ---- FID: fp64 activation moments and the products of the Frechet distance (fid.hip) ---------------------------------
+ * The image variants' validation metric (soft_intro_vae/train_soft_intro_vae.py:283-296 calls
+ * metrics/fid_score.py::calculate_fid_given_dataset), everything but the Inception network.  All arithmetic is fp64 on
+ * v_mfma_f64_16x16x4_f64; one block owns each 64 x 64 output tile and walks the summed index in ascending order: no
+ * atomics, two runs are bit-identical.  Every pointer must be aligned for its element type (SIVAE_ERR_SHAPE).
+ *
+ * sivae_fid_moments replaces the host-side activation store and np.mean / np.cov of fid_score.py:197, :202-203, :262-265,
+ * :349-350, :375-376: A [n][d] float32 (row stride in elements, >= d; unit column stride), each element converted to
+ * fp64 on load; G [d][d] (contiguous fp64) += A^T A on the 64 x 64 block tiles with column tile >= row tile (the tiles
+ * below are never touched; inside a diagonal tile both halves are computed and are bit-identical mirrors), s [d]
+ * (fp64) += column sums, rows added in ascending order.  Rows >= n and columns >= d are masked, not read.  Any n >= 0
+ * (n = 0 launches nothing); 1 <= d <= 8192, SIVAE_ERR_SHAPE otherwise. */
+int sivae_fid_moments(const float* A, long long row_stride, int n, int d, double* G, double* s, sivae_stream_t stream);
+/* The statistics of (n, s, G) (fid_score.py:349-350): mu [d] = s / n, sigma [d][d] = (G - s s^T / n) / (n - 1) written as
+ * the full symmetric matrix from G's entries on and above the diagonal (exactly symmetric).  n = 1 gives NaN in sigma,
+ * as np.cov does; n <= 0 is SIVAE_ERR_SHAPE. */
+int sivae_fid_finalize(const double* G, const double* s, long long n, int d, double* mu, double* sigma,
+                       sivae_stream_t stream);
+/* C [M][N] = X^T Y for fp64 X [K][M], Y [K][N] (row strides ldx >= M, ldy >= N, ldc >= N in elements; C must not
+ * overlap X or Y): the products behind the matrix square root of fid_score.py:307.  symmetric = 1 (M == N, for a product
+ * that is symmetric by construction): only the tiles with column tile >= row tile are computed and every entry on or
+ * above the diagonal is stored at (i, j) and (j, i), so C is exactly symmetric.  K >= 1, 1 <= M, N <= 8192
+ * (SIVAE_ERR_SHAPE); SIVAE_ERR_MODE for a flag that is not 0 or 1. */
+int sivae_fid_xty_f64(const double* X, long long ldx, const double* Y, long long ldy, double* C, long long ldc, int K,
+                      int M, int N, int symmetric, sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

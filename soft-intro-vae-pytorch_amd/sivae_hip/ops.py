@@ -1295,6 +1295,88 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999
               float(beta1), float(beta2), float(eps), float(bc2 ** 0.5), float(grad_scale), _s())
 
 
+# ------------------------------------------------------------------------------------------------ FID (fid.hip)
+FID_MAX_DIMS = 8192
+
+
+def _require_f64(who, *tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("sivae_hip.%s: tensor is on %s — the FID kernels need a ROCm device tensor and have no "
+                               "CPU fallback" % (who, t.device))
+        if t.dtype != torch.float64:
+            raise TypeError("sivae_hip.%s: expected float64, got %s" % (who, t.dtype))
+
+
+def fid_state(d, device):
+    """-> (G [d, d], s [d]): a zeroed fp64 moment state (sivae_hip.fid.ActivationStatistics holds one)"""
+    if not 1 <= int(d) <= FID_MAX_DIMS:
+        raise ValueError("sivae_hip.fid_state: dims must be in 1 .. %d, got %d" % (FID_MAX_DIMS, d))
+    return (torch.zeros((int(d), int(d)), dtype=torch.float64, device=device),
+            torch.zeros(int(d), dtype=torch.float64, device=device))
+
+
+def fid_state_copy(G, s):
+    """-> copies of a moment state"""
+    _require_f64("fid_state_copy", G, s)
+    G2, s2 = torch.empty_like(G), torch.empty_like(s)
+    G2.copy_(G)
+    s2.copy_(s)
+    return G2, s2
+
+
+def fid_staging(rows, d, device):
+    """-> a [rows, d] fp32 staging buffer for activation rows"""
+    return torch.empty((int(rows), int(d)), dtype=torch.float32, device=device)
+
+
+def fid_moments(a, n, G, s):
+    """G += a[:n]^T a[:n] on the 64 x 64 block tiles on and above the diagonal, s += the column sums of a[:n]; a: fp32
+    [rows >= n, d] with unit column stride (any row stride), converted to fp64 on load.  In place, returns nothing."""
+    if not a.is_cuda or a.dtype != torch.float32 or a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
+        raise TypeError("sivae_hip.fid_moments: expected a 2-D float32 ROCm tensor with unit column stride")
+    _require_f64("fid_moments", G, s)
+    d = a.shape[1]
+    if not 0 <= int(n) <= a.shape[0] or tuple(G.shape) != (d, d) or tuple(s.shape) != (d,) or \
+            not (G.is_contiguous() and s.is_contiguous()):
+        raise ValueError("sivae_hip.fid_moments: n rows of a [rows, d] go into contiguous G [d, d] and s [d]")
+    t0 = timer_begin()
+    _lib.call("sivae_fid_moments", _p(a), int(a.stride(0)) if a.shape[0] > 1 else d, int(n), d, _p(G), _p(s),
+              _s(a))
+    if t0 is not None:
+        timer_end(t0, "fid_moments", float(n) * d * (d + 1))
+
+
+def fid_finalize(G, s, n):
+    """-> (mu [d], sigma [d, d]) fp64: mu = s / n, sigma = (G - s s^T / n) / (n - 1), exactly symmetric"""
+    _require_f64("fid_finalize", G, s)
+    d = s.shape[0]
+    if tuple(G.shape) != (d, d) or not (G.is_contiguous() and s.is_contiguous()) or int(n) < 1:
+        raise ValueError("sivae_hip.fid_finalize: contiguous G [d, d], s [d] and n >= 1 rows")
+    mu = torch.empty(d, dtype=torch.float64, device=G.device)
+    sigma = torch.empty((d, d), dtype=torch.float64, device=G.device)
+    _lib.call("sivae_fid_finalize", _p(G), _p(s), int(n), d, _p(mu), _p(sigma), _s(G))
+    return mu, sigma
+
+
+def fid_xty(x, y, symmetric=False):
+    """-> x^T y [M, N] fp64 for x [K, M], y [K, N] (unit column stride); symmetric=True (M == N, a product symmetric by
+    construction) computes the tiles on and above the diagonal and mirrors them: the result is exactly symmetric"""
+    _require_f64("fid_xty", x, y)
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0] or \
+            (x.shape[1] > 1 and x.stride(1) != 1) or (y.shape[1] > 1 and y.stride(1) != 1):
+        raise ValueError("sivae_hip.fid_xty: x [K, M] and y [K, N] with unit column stride")
+    K, M = x.shape
+    N = y.shape[1]
+    out = torch.empty((M, N), dtype=torch.float64, device=x.device)
+    t0 = timer_begin()
+    ldx, ldy = (int(x.stride(0)), int(y.stride(0))) if K > 1 else (M, N)
+    _lib.call("sivae_fid_xty_f64", _p(x), ldx, _p(y), ldy, _p(out), N, K, M, N, int(bool(symmetric)), _s(x))
+    if t0 is not None:
+        timer_end(t0, "fid_xty_sym" if symmetric else "fid_xty", (1.0 if symmetric else 2.0) * K * M * N)
+    return out
+
+
 class _SwitchWatch(type(sys)):
     """this module's type: assigning any of its attributes (ops.WINO4 = False, monkeypatch.setattr(ops, ...), dp's
     ops.SYNC_BN = sync) forgets the memoised routes"""

@@ -187,6 +187,36 @@ def _require_device(device, local_rank=None):
     return device
 
 
+# ---- FID (reference :283-296) ------------------------------------------------------------------------------
+# SIVAE_FID=device (default): sivae_hip.fid, moments and distance on the device; SIVAE_FID=reference: the reference's
+# metrics.fid_score pass, unchanged (host-side activation store, np.cov, scipy's sqrtm).
+# SIVAE_FID_CACHE_REAL=1 (default 0): the real-side statistics of the first pass serve the later passes.  The reference
+# recomputes them every pass on whatever 50 000 images its shuffled loader yields first, hence off by default.
+FID_ARGS = dict(dims=2048, num_images=50000)  # what the reference's call passes (:287-288)
+FID_INCEPTION = None  # a feature network instead of the reference's InceptionV3 (a module whose call returns [features])
+
+
+def _calculate_fid(loader, model, batch_size, device, real_stats):
+    mode = os.environ.get("SIVAE_FID", "device")
+    if mode == "reference":
+        from metrics.fid_score import calculate_fid_given_dataset  # the reference's metrics package
+        return calculate_fid_given_dataset(loader, model, batch_size, cuda=True, dims=FID_ARGS["dims"], device=device,
+                                           num_images=FID_ARGS["num_images"])
+    if mode != "device":
+        raise ValueError("SIVAE_FID must be 'device' or 'reference', got %r" % mode)
+    from sivae_hip import fid as _fid
+    dims, num_images = FID_ARGS["dims"], FID_ARGS["num_images"]
+    inception = FID_INCEPTION if FID_INCEPTION is not None else _fid.reference_inception(dims)
+    inception.to(device)
+    stats = real_stats.get("stats")
+    if stats is None:
+        stats = _fid.real_statistics(loader, inception, dims, device, num_images)
+        if os.environ.get("SIVAE_FID_CACHE_REAL", "0") == "1":
+            real_stats["stats"] = stats
+    return _fid.calculate_fid_given_dataset(loader, model, batch_size, cuda=True, dims=dims, device=device,
+                                            num_images=num_images, inception=inception, real_stats=stats)
+
+
 def train_soft_intro_vae(dataset="cifar10", z_dim=128, lr_e=2e-4, lr_d=2e-4, batch_size=128, num_workers=4,
                          start_epoch=0, exit_on_negative_diff=False,
                          num_epochs=250, num_vae=0, save_interval=50, recon_loss_type="mse",
@@ -276,16 +306,15 @@ def _train(dataset, z_dim, lr_e, lr_d, batch_size, num_workers, start_epoch, exi
     cur_iter = 0
     hist = {k: [] for k in ("kl_real", "kl_fake", "kl_rec", "rec_err", "exp_elbo_f", "exp_elbo_r")}
     best_fid = None
+    fid_real_stats = {}  # SIVAE_FID_CACHE_REAL=1: the first FID pass's real-side (mu, sigma)
     real_batch = None
     for epoch in range(start_epoch, num_epochs):
         if sampler is not None:
             sampler.set_epoch(epoch)
         if main_rank and with_fid and ((epoch == 0) or (epoch >= 100 and epoch % 20 == 0) or epoch == num_epochs - 1):
-            from metrics.fid_score import calculate_fid_given_dataset  # the reference's metrics package
             with torch.no_grad():
                 print("calculating fid...")
-                fid = calculate_fid_given_dataset(loader, model, batch_size, cuda=True, dims=2048, device=device,
-                                                  num_images=50000)
+                fid = _calculate_fid(loader, model, batch_size, device, fid_real_stats)
                 print("fid:", fid)
                 if best_fid is None:
                     best_fid = fid
