@@ -806,6 +806,37 @@ int sivae_emd_matrix(const float* sample, long long sample_stride_s, long long s
                      const float* ref, long long ref_stride_s, long long ref_stride_n, long long ref_stride_c, float* D,
                      int S, int R, int M, int N, int s0, int s1, int normalize, void* workspace, size_t workspace_bytes,
                      sivae_stream_t stream);
+/* The same quantity as a reconstruction loss (reference: soft_intro_vae_3d/train_soft_intro_vae_3d.py:171-176 accepts
+ * 'earth_mover' next to 'chamfer'; the project it derives from trains with losses/earth_mover_distance.py::EMD on the
+ * approxmatch / matchcost / matchcostgrad extension).  For a batch of cloud pairs left [B][N][3] and right [B][M][3]
+ * (float32, element strides as above, 1 <= N, M <= 4096):
+ *   cost[b] = EMD(left = left_b, right = right_b), exactly the quantity above (ten levels, steps 1 - 3, the direct-form
+ *   d2, big = max(N, M)): with t_j(k, l) the step-3 weight of level j, cost = sum_j sum_kl t_j(k, l) sqrt(d2(k, l)),
+ *   divided by big when normalize.  cost[b] is bit for bit the D[0][0] of sivae_emd_matrix(sample = right_b, ref = left_b).
+ * The gradient is matchcostgrad's: the plan t is HELD CONSTANT (it is not the derivative through the ratios),
+ *   dleft[b][k]  =   sum_j sum_l t_j(k, l) (A_k - B_l) / sqrt(d2(k, l))
+ *   dright[b][l] = - sum_j sum_k t_j(k, l) (A_k - B_l) / sqrt(d2(k, l))
+ * both divided by big when normalize.  A pair with d2 == 0 contributes zero: the reciprocal root is taken of
+ * max(d2, FLT_MIN) (the original's max(d, 1e-20)) and the difference is zero there.  Because the plan moves with the
+ * points, finite differences of cost do NOT reproduce these gradients (torch.autograd.gradcheck does not apply); with the
+ * plan fixed the cost is 1-homogeneous, so sum_k A_k . dleft[k] + sum_l B_l . dright[l] = cost, and the two gradients sum
+ * to zero per coordinate.
+ * The order is the original's: EMD()(preds, gts) has left = preds, right = gts.
+ * dleft (contiguous [B][N][3]) and dright (contiguous [B][M][3]) may each be NULL: only the sums asked for are formed (the
+ * left one rides on the step-3 sweep, the right one takes a fourth sweep per level, own l over staged k, forming the same
+ * t = (w ratioL[k]) ratioR[l] in the same order).  If pair b has a NaN or infinite coordinate, cost[b] and every element
+ * of both gradient slices of b are NaN, written outright; no other pair changes a bit.  No atomics: every per-point sum
+ * of a level is fp32 in index order, the levels are added in level order, the cost total is formed as above; every
+ * output element is written once.  Two runs are bit-identical, whatever the grid, the batch split or the strides.
+ * SIVAE_ERR_NULL for a missing left / right / cost, SIVAE_ERR_SHAPE for a non-positive size, SIVAE_ERR_RANGE beyond
+ * 4096 points or for 3 B max(N, M) >= 2^31 - 1, SIVAE_ERR_MODE for a normalize other than 0 / 1, SIVAE_ERR_WORKSPACE
+ * for a NULL or too small workspace: all returned before any device call.  No workspace is used: the size is 0, the
+ * pointer must still not be NULL. */
+size_t sivae_emd_loss_workspace_bytes(int B, int N, int M);
+int sivae_emd_loss(const float* left, long long left_stride_b, long long left_stride_n, long long left_stride_c,
+                   const float* right, long long right_stride_b, long long right_stride_n, long long right_stride_c,
+                   float* cost, float* dleft, float* dright, int B, int N, int M, int normalize, void* workspace,
+                   size_t workspace_bytes, sivae_stream_t stream);
 
 /* ---- FID: fp64 activation moments and the products of the Frechet distance (fid.hip) ---------------------------------
  * The image variants' validation metric (soft_intro_vae/train_soft_intro_vae.py:283-296 calls

@@ -2,6 +2,8 @@
 csrc/pointcloud.hip: tensor-level wrappers in the style of `ops` and the autograd Functions on top of them.
 
   chamfer_distance(preds [B, M, 3], gts [B, N, 3]) -> [B]       losses/chamfer_loss.py:11-17 (direct-form distances)
+  emd_distance(preds [B, N, 3], gts [B, M, 3])     -> [B]       the loop's 'earth_mover' loss: emd_matrix's quantity with
+                                                                 matchcostgrad's gradients (csrc/pc_emd.hip)
   relu_bn(a [B, C, N], weight, bias, BNState)      -> [B, C, N]  nn.ReLU -> nn.BatchNorm1d, relu(a) never stored
   max_points(y [B, C, N])                          -> [B, C]     y.max(dim=2)[0]
   relu_bn_max(a [B, C, N], weight, bias, BNState)  -> [B, C]     max_points(relu_bn(a)) in one piece: neither y nor the
@@ -474,6 +476,54 @@ def emd_matrix(sample, ref, normalize=True):
     return D
 
 
+# ------------------------------------------------------------------------------------------------ the earth mover's loss
+# Point pairs (cloud pairs x N x M) one launch of emd_loss_fwd may cover.  The loss kernel takes up to 256 registers a
+# lane, so ONE block is resident on a compute unit: 2^30 is 256 cloud pairs of 2048 points, one round of resident blocks on
+# the 256 compute units.  A training batch (32 - 64 pairs) is one launch.
+# Measured on an MI355X (tools/bench_pc_emd.py --step loss, profiles/pc_emd_loss_bench.txt), 32 pairs of 2048 points:
+# one launch, 7.72 ms for the cost alone, 11.55 ms with dright, 14.34 ms with both gradients; 256 pairs, one on every
+# compute unit, both gradients: 14.47 ms at the longest (chamfer_matrix's launches take 19 - 22 ms).
+EMD_LOSS_POINT_PAIRS_PER_LAUNCH = 1 << 30
+
+
+def emd_loss_fwd(left, right, want_dleft, want_dright, normalize=False):
+    """left [B, N, 3], right [B, M, 3] (float32, any strides, at most 4096 points a cloud) -> (cost [B], dleft [B, N, 3] or
+    None, dright [B, M, 3] or None): cost[b] = EMD(left = left_b, right = right_b), the quantity of emd_matrix (bit for bit
+    emd_matrix(right[b:b+1], left[b:b+1])[0, 0]), and matchcostgrad's gradients of it, the plan held constant
+    (include/sivae_hip.h).  Only the gradients asked for are computed.  A pair with a non-finite coordinate gets a NaN
+    cost and NaN gradient slices; no other pair changes."""
+    for pcs in (left, right):  # (the shape error before the device's, as emd_matrix does)
+        if pcs.dim() != 3 or pcs.shape[2] != 3:
+            raise ValueError("sivae_hip.emd_loss: expected point clouds [B, N, 3], got %s" % (tuple(pcs.shape),))
+    B, N, sl = _require_clouds(left, "emd_loss")
+    Br, M, sr = _require_clouds(right, "emd_loss")
+    if B != Br:
+        raise ValueError("sivae_hip.emd_loss: %d left clouds against %d right clouds" % (B, Br))
+    if left.device != right.device:
+        raise ValueError("sivae_hip.emd_loss: left is on %s, right on %s" % (left.device, right.device))
+    if N > EMD_MAX_POINTS or M > EMD_MAX_POINTS:
+        raise ValueError("sivae_hip.emd_loss: clouds of %d and %d points, at most %d are supported" % (N, M, EMD_MAX_POINTS))
+    if 3 * B * max(N, M) >= 0x7fffffff:
+        raise ValueError("sivae_hip.emd_loss: %d clouds of %d points do not fit an int32 index" % (B, max(N, M)))
+    cost = torch.empty(B, dtype=torch.float32, device=left.device)
+    dleft = torch.empty((B, N, 3), dtype=torch.float32, device=left.device) if want_dleft else None
+    dright = torch.empty((B, M, 3), dtype=torch.float32, device=left.device) if want_dright else None
+    slab = max(1, min(B, EMD_LOSS_POINT_PAIRS_PER_LAUNCH // (N * M)))
+    ws = workspace(_lib.load().sivae_emd_loss_workspace_bytes(slab, N, M), left.device)
+    for b0 in range(0, B, slab):
+        b1 = min(B, b0 + slab)
+        # a pair's results do not depend on which launch computes them: to the library a slab is a batch of its own
+        t0 = timer_begin()
+        _lib.call("sivae_emd_loss", _p(left[b0:b1]), sl[0], sl[1], sl[2], _p(right[b0:b1]), sr[0], sr[1], sr[2],
+                  _p(cost[b0:b1]), _p(dleft[b0:b1]) if want_dleft else None, _p(dright[b0:b1]) if want_dright else None,
+                  b1 - b0, N, M, int(bool(normalize)), _p(ws), ws.numel(), _s(left))
+        if t0 is not None:
+            # per point pair: the thirty sweeps of emd_matrix (300), the left gradient on the third sweep of a level (7 a
+            # level), the right gradient's fourth sweep (24 a level)
+            timer_end(t0, "emd_loss_kernel", (300.0 + 70.0 * bool(want_dleft) + 240.0 * bool(want_dright)) * (b1 - b0) * N * M)
+    return cost, dleft, dright
+
+
 # ------------------------------------------------------------------------------------------------ autograd
 class ChamferFn(torch.autograd.Function):
     @staticmethod
@@ -490,6 +540,35 @@ class ChamferFn(torch.autograd.Function):
         preds, gts, idx_p, idx_g = ctx.saved_tensors
         need = ctx.needs_input_grad
         return chamfer_bwd(g.contiguous(), preds, gts, idx_p, idx_g, need[0], need[1])
+
+
+class EmdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, preds, gts, normalize):
+        need = ctx.needs_input_grad
+        # (any strides are read in place: the training loop passes x.permute(0, 2, 1) + 0.5 and the decoder's view)
+        cost, dpreds, dgts = emd_loss_fwd(preds, gts, need[0], need[1], normalize)
+        ctx.save_for_backward(dpreds, dgts)
+        return cost
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        dpreds, dgts = ctx.saved_tensors
+        g = g.contiguous()
+        _require_f32(g)
+        g = g.view(-1, 1, 1)
+        return (None if dpreds is None else g * dpreds), (None if dgts is None else g * dgts), None
+
+
+def emd_distance(preds, gts, normalize=False):
+    """per-cloud approximate-matching earth mover's distance [B] of preds [B, N, 3] (the matching's left side) and gts
+    [B, M, 3] (its right side), the original's EMD()(preds, gts): emd_loss_fwd's cost, differentiable in both arguments
+    with matchcostgrad's gradients (the plan held constant), divided by max(N, M) when normalize.  The forward computes the
+    gradients the inputs need and the backward scales them by the upstream g[b]: a second derivative raises.
+    torch.autograd.gradcheck does NOT apply: the plan moves with the points, so finite differences of the cost are not the
+    gradient returned here."""
+    return EmdFn.apply(preds, gts, bool(normalize))
 
 
 def chamfer_distance(preds, gts, return_indices=False):

@@ -19,12 +19,21 @@ that fails):
   full   the whole 2400 x 800 matrix ONCE, each launch timed (the longest single launch is what
          pointcloud.EMD_POINT_PAIRS_PER_LAUNCH bounds).
 
+  loss   NOT part of the driver: the reconstruction loss `pointcloud.emd_distance` (emd_loss_kernel), 32 pairs of 2048-point
+         clouds.  (a) forward + backward with the gradient of the second argument only, as training asks, alternating
+         round by round with the torch restatement ON THE SAME PAIRS, its plan detached and autograd on; (b) the cost of
+         the gradients: emd_matrix over 32 cloud pairs of the same sizes (one sample cloud against the 32 left clouds, one
+         launch), then emd_loss_fwd with no gradient, with dright, with both, every launch timed; (c) the longest launch
+         EMD_LOSS_POINT_PAIRS_PER_LAUNCH allows at this size (256 pairs of 2048 points, both gradients).  It appends its
+         line to its own file, profiles/pc_emd_loss_bench.txt (--loss-out).
+
 Each step prints one JSON line; the driver appends the raw lines to profiles/pc_emd_bench.txt.
 
     python tools/bench_pc_emd.py [--out profiles/pc_emd_bench.txt]        # the driver: all three steps
     python tools/bench_pc_emd.py --step ab [--sample 240] [--ref 800] [--points 2048] [--rounds 5] [--baseline-pairs 32]
     python tools/bench_pc_emd.py --step slab [--points 2048] [--rounds 5]
     python tools/bench_pc_emd.py --step full [--sample 2400] [--ref 800] [--points 2048]
+    python tools/bench_pc_emd.py --step loss [--pairs 32] [--points 2048] [--rounds 5] [--loss-out FILE]
 """
 import argparse
 import json
@@ -78,36 +87,47 @@ def _rates(res, S, R, M, N, ms, cus):
     res["valu_lane_slots_per_weight_at_clock"] = round(cus * 64 * res["clock_mhz"] * 1e6 / res["weights_per_s"], 3)
 
 
-def torch_emd(torch, sample, ref, normalize=True):
-    """the ten levels in plain torch ops: sample [M, 3] (right), ref [P, N, 3] (left) -> [P] float32"""
-    P, n, m = ref.shape[0], ref.shape[1], sample.shape[0]
-    diff = ref[:, :, None, :] - sample[None, None, :, :]                       # [P, n, m, 3]
+def torch_emd(torch, sample, ref, normalize=True, detach_plan=False):
+    """the ten levels in plain torch ops: sample [M, 3] or [P, M, 3] (right), ref [P, N, 3] (left) -> [P] float32.
+    detach_plan: the levels run without autograd and the cost is sum(plan * dist) with the plan a constant, so that
+    autograd yields matchcostgrad's gradient (what emd_distance returns)"""
+    P, n, m = ref.shape[0], ref.shape[1], sample.shape[-2]
+    right = sample if sample.dim() == 3 else sample[None]
+    diff = ref[:, :, None, :] - right[:, None, :, :]                           # [P, n, m, 3]
     d2 = diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1] + diff[..., 2] * diff[..., 2]
     del diff
     dist = d2.sqrt()
     big = float(max(n, m))
-    remL = torch.full((P, n), big / n, dtype=torch.float32, device=ref.device)
-    remR = torch.full((P, m), big / m, dtype=torch.float32, device=ref.device)
     cost = torch.zeros(P, dtype=torch.float64, device=ref.device)
-    for j in range(7, -3, -1):
-        w = torch.exp(d2 * (-(4.0 ** j) if j > -2 else 0.0))
-        ratioL = remL / (1e-9 + (w * remR[:, None, :]).sum(2))
-        sumr = remR * (w * ratioL[:, :, None]).sum(1)
-        ratioR = remR * torch.clamp(remR / (sumr + 1e-9), max=1.0)
-        remR = torch.clamp(remR - sumr, min=0.0)
-        w = w * ratioL[:, :, None] * ratioR[:, None, :]                        # (the plan of this level)
-        cost += (w * dist).sum((1, 2), dtype=torch.float64)
-        remL = torch.clamp(remL - w.sum(2), min=0.0)
+    with torch.set_grad_enabled(torch.is_grad_enabled() and not detach_plan):
+        if detach_plan:
+            d2, plan = d2.detach(), torch.zeros_like(d2)
+        remL = torch.full((P, n), big / n, dtype=torch.float32, device=ref.device)
+        remR = torch.full((P, m), big / m, dtype=torch.float32, device=ref.device)
+        for j in range(7, -3, -1):
+            w = torch.exp(d2 * (-(4.0 ** j) if j > -2 else 0.0))
+            ratioL = remL / (1e-9 + (w * remR[:, None, :]).sum(2))
+            sumr = remR * (w * ratioL[:, :, None]).sum(1)
+            ratioR = remR * torch.clamp(remR / (sumr + 1e-9), max=1.0)
+            remR = torch.clamp(remR - sumr, min=0.0)
+            w = w * ratioL[:, :, None] * ratioR[:, None, :]                    # (the plan of this level)
+            if detach_plan:
+                plan += w
+            else:
+                cost += (w * dist).sum((1, 2), dtype=torch.float64)
+            remL = torch.clamp(remL - w.sum(2), min=0.0)
+    if detach_plan:
+        cost = (plan * dist).sum((1, 2), dtype=torch.float64)
     return (cost / big if normalize else cost).float()
 
 
-def _time_launches(torch, PC, fn):
-    """-> (result, total ms, [ms of each sivae_emd_matrix launch])"""
+def _time_launches(torch, PC, fn, entry="sivae_emd_matrix"):
+    """-> (result, total ms, [ms of each launch of `entry`])"""
     launches = []
     real = PC._lib.call
 
     def call(name, *args):
-        if name != "sivae_emd_matrix":
+        if name != entry:
             return real(name, *args)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -213,6 +233,73 @@ def step_full(a):
     print(json.dumps(res))
 
 
+def step_loss(a):
+    import torch
+    from sivae_hip import pointcloud as PC
+    B, n = a.pairs, a.points
+    g = torch.Generator().manual_seed(0)
+    dev = torch.device("cuda:0")
+    gts = (torch.rand(B, n, 3, generator=g) - 0.5).to(dev)        # the loss's first argument (left), no gradient
+    rec = (torch.rand(B, n, 3, generator=g) - 0.5).to(dev)        # its second (right): the decoder's output
+
+    def fwd_bwd(loss_of):
+        x = rec.clone().requires_grad_(True)
+        loss_of(gts, x).sum().backward()
+        return x.grad
+
+    def new():
+        return fwd_bwd(lambda l, r: PC.emd_distance(l, r))
+
+    def baseline():
+        return fwd_bwd(lambda l, r: torch_emd(torch, r, l, normalize=False, detach_plan=True))
+
+    g1, g0 = new(), baseline()  # (warm-up of both forms)
+    torch.cuda.synchronize()
+    rel = float((g1.double() - g0.double()).abs().max() / g0.double().abs().max())
+    ab = dict(new=[], baseline=[])
+    for _ in range(a.rounds):
+        for name, fn in (("new", new), ("baseline", baseline)):
+            ab[name].append(_timed(torch, fn)[1])
+    res = dict(step="loss", pairs=B, points=n, rounds=a.rounds, **_device(torch))
+    res["fwd_bwd_dright_only"], res["torch_plan_detached_fwd_bwd"] = _stats(ab["new"]), _stats(ab["baseline"])
+    spread = res["torch_plan_detached_fwd_bwd"]["max_ms"] - res["torch_plan_detached_fwd_bwd"]["min_ms"]
+    res["torch_spread_ms"] = round(spread, 3)
+    res["gain_ms"] = round(res["torch_plan_detached_fwd_bwd"]["median_ms"] - res["fwd_bwd_dright_only"]["median_ms"], 3)
+    res["new_wins"] = bool(res["gain_ms"] > spread)
+    res["speedup"] = round(res["torch_plan_detached_fwd_bwd"]["median_ms"] / res["fwd_bwd_dright_only"]["median_ms"], 1)
+    res["max_rel_diff_dright_new_vs_torch_autograd"] = rel
+    # the cost of the gradients, every launch timed
+    forms = (("emd_matrix_1x%d" % B, "sivae_emd_matrix", lambda: PC.emd_matrix(rec[:1], gts, normalize=False)),
+             ("cost_only", "sivae_emd_loss", lambda: PC.emd_loss_fwd(gts, rec, False, False)),
+             ("with_dright", "sivae_emd_loss", lambda: PC.emd_loss_fwd(gts, rec, False, True)),
+             ("with_both", "sivae_emd_loss", lambda: PC.emd_loss_fwd(gts, rec, True, True)))
+    times = {name: [] for name, _, _ in forms}
+    for name, _, fn in forms:
+        fn()  # (warm-up)
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for name, entry, fn in forms:
+            _, _, per_launch = _time_launches(torch, PC, fn, entry)
+            times[name] += per_launch
+    res["launch_ms"] = {name: _stats(v) for name, v in times.items()}
+    # the longest launch the cap allows at this size: one cloud pair on every compute unit, both gradients
+    full = max(1, PC.EMD_LOSS_POINT_PAIRS_PER_LAUNCH // (n * n))
+    gts_full, rec_full = gts.repeat((full + B - 1) // B, 1, 1)[:full], rec.repeat((full + B - 1) // B, 1, 1)[:full]
+    PC.emd_loss_fwd(gts_full, rec_full, True, True)
+    torch.cuda.synchronize()
+    full_ms = []
+    for _ in range(a.rounds):
+        full_ms += _time_launches(torch, PC, lambda: PC.emd_loss_fwd(gts_full, rec_full, True, True), "sivae_emd_loss")[2]
+    res["full_round"] = dict(pairs=full, launches_per_call=len(full_ms) // a.rounds, with_both=_stats(full_ms))
+    res["launches_per_call"] = {name: len(v) // a.rounds for name, v in times.items()}
+    res["longest_launch_ms"] = round(max(full_ms), 3)
+    res["point_pairs_per_launch"] = PC.EMD_LOSS_POINT_PAIRS_PER_LAUNCH
+    print(json.dumps(res))
+    out = a.loss_out if os.path.isabs(a.loss_out) else os.path.join(REPO, a.loss_out)
+    with open(out, "a") as f:
+        f.write(json.dumps(res) + "\n")
+
+
 def drive(a):
     out = a.out if os.path.isabs(a.out) else os.path.join(REPO, a.out)
     for step in ("ab", "slab", "full"):
@@ -229,7 +316,7 @@ def drive(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=("ab", "slab", "full"))
+    ap.add_argument("--step", choices=("ab", "slab", "full", "loss"))
     ap.add_argument("--sample", type=int, default=0, help="sample clouds (default: 240 for ab, 2400 for full)")
     ap.add_argument("--ref", type=int, default=800)
     ap.add_argument("--points", type=int, default=2048)
@@ -237,13 +324,15 @@ def main():
     ap.add_argument("--baseline-pairs", type=int, default=32, help="cloud pairs the torch restatement is timed on")
     ap.add_argument("--clock-mhz", type=float, default=2400.0, help="engine clock the VALU issue rate is quoted at")
     ap.add_argument("--out", default=os.path.join("profiles", "pc_emd_bench.txt"))
+    ap.add_argument("--pairs", type=int, default=32, help="cloud pairs of the loss step (a training batch)")
+    ap.add_argument("--loss-out", default=os.path.join("profiles", "pc_emd_loss_bench.txt"))
     a = ap.parse_args()
     if a.step is None:
         return drive(a)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_pc_emd: needs a ROCm device (timings on a CPU would say nothing)")
-    dict(ab=step_ab, slab=step_slab, full=step_full)[a.step](a)
+    dict(ab=step_ab, slab=step_slab, full=step_full, loss=step_loss)[a.step](a)
 
 
 if __name__ == "__main__":
