@@ -864,6 +864,45 @@ int sivae_fid_finalize(const double* G, const double* s, long long n, int d, dou
 int sivae_fid_xty_f64(const double* X, long long ldx, const double* Y, long long ldy, double* C, long long ldc, int K,
                       int M, int N, int symmetric, sivae_stream_t stream);
 
+/* ---- pairwise figures on the FID features: precision / recall, density / coverage, KID (feat_pairs.hip) --------------
+ * Everything is a reduction over X Y^T of two sets of feature rows, float32 [n][d] with unit column stride and any row
+ * stride (ld >= d, in elements), every element converted to fp64 on load; 1 <= d <= 8192, n >= 1 (SIVAE_ERR_SHAPE).  One
+ * tile body computes a 64 x 64 tile of X Y^T on v_mfma_f64_16x16x4_f64, the summed index ascending; rows are read with
+ * 16-byte loads where the base is 16-byte aligned and ld % 4 == 0, with scalar loads otherwise.  The squared distance is
+ *   sqdist(x, y) = max(0, |x|^2 + |y|^2 - 2 x.y)            (fp64 throughout; the products of fp32 values are exact)
+ * with the squared norms of sivae_feat_row_sqnorm, so |sqdist - sum_k (x_k - y_k)^2| <= 2 (d + 3) 2^-53 (|x| + |y|)^2:
+ * two equal rows give a distance within that bound of 0, not exactly 0.  Inputs must be finite (the callers check the
+ * norms).  No atomics: every output element has one owner, and two runs are bit-identical.  Pointers must be aligned
+ * for their element type (SIVAE_ERR_SHAPE).
+ *
+ * out[i] = sum_k X[i][k]^2, k ascending. */
+int sivae_feat_row_sqnorm(const float* X, long long ld, int n, int d, double* out, sivae_stream_t stream);
+/* D[i][j] = sqdist(x_i, y_j), D [nx][ny] fp64 with row stride ldd >= ny: the plain matrix, for sets small enough to hold
+ * it; one block per output tile.  SIVAE_ERR_RANGE above 2^31 - 1 tiles. */
+int sivae_feat_sqdist(const float* X, long long ldx, int nx, const double* nrmx, const float* Y, long long ldy, int ny,
+                      const double* nrmy, int d, double* D, long long ldd, sivae_stream_t stream);
+/* best [nx][k] fp64, every row ascending (+inf before the first call): row i <- the k smallest of its values and
+ * sqdist(x_i, y_j) for j in [c0, c1), 0 <= c0 <= c1 <= ny; with self = 1 the pair j == i is left out by index, not by
+ * value.  1 <= k <= 8.  One block owns 64 rows of X and walks the columns: the state lives in `best` so that the caller
+ * can cut [0, ny) into launches, and since merging smallest values is exact the result is the same for every cutting. */
+int sivae_feat_knn_update(const float* X, long long ldx, int nx, const double* nrmx, const float* Y, long long ldy, int ny,
+                          const double* nrmy, int c0, int c1, int d, int k, int self, double* best,
+                          sivae_stream_t stream);
+/* count[j] += #{ i in [c0, c1) : sqdist(q_j, x_i) <= radius[i] }, count int32 [nq], radius fp64 [nx], 0 <= c0 <= c1 <=
+ * nx: in how many of the balls around the rows of X the row q_j lies.  One block owns 64 rows of Q; exact for every
+ * cutting of [0, nx). */
+int sivae_feat_within_update(const float* Q, long long ldq, int nq, const double* nrmq, const float* X, long long ldx,
+                             int nx, const double* nrmx, const double* radius, int c0, int c1, int d, int* count,
+                             sivae_stream_t stream);
+/* out[s] = sum_{i < m, j < n} (gamma x_si . y_sj + coef0)^degree for the S subsets X [S][m][d], Y [S][n][d] (subset
+ * strides in elements), i == j left out with skip_diag = 1; degree 1 .. 4 by repeated multiplication (SIVAE_ERR_MODE).
+ * One block per (subset, 64-row strip) adds its entries in a fixed order into the workspace, a second launch adds the
+ * strips of a subset in ascending order: a subset's sum does not depend on the other subsets of the launch. */
+size_t sivae_feat_poly_workspace_bytes(int S, int m);
+int sivae_feat_poly_sums(const float* X, long long x_stride_s, long long ldx, const float* Y, long long y_stride_s,
+                         long long ldy, int S, int m, int n, int d, double gamma, double coef0, int degree, int skip_diag,
+                         double* out, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

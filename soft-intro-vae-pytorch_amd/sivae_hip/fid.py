@@ -27,6 +27,21 @@ from . import infer, ops
 EIGH = os.environ.get("SIVAE_FID_EIGH", "device")
 
 
+def activation_rows(act, dims):
+    """what `ActivationStatistics.update` accepts -> rows [b, dims]: [b, d], [b, d, 1, 1] or [b, d, h, w] (averaged over
+    h, w) float32 on the device"""
+    if not isinstance(act, torch.Tensor) or not act.is_cuda or act.dtype != torch.float32:
+        raise TypeError("sivae_hip.fid: activations must be a float32 ROCm tensor (no CPU fallback)")
+    if act.dim() == 4:
+        if act.shape[2] != 1 or act.shape[3] != 1:  # fid_score.py:195-196
+            act = torch.nn.functional.adaptive_avg_pool2d(act, output_size=(1, 1))
+        act = act.reshape(act.shape[0], -1)
+    if act.dim() != 2 or act.shape[1] != dims:
+        raise ValueError("sivae_hip.fid: expected activations [b, %d], [b, %d, 1, 1] or [b, %d, h, w], got %s"
+                         % (dims, dims, dims, tuple(act.shape)))
+    return act
+
+
 class ActivationStatistics:
     """Running first and second moments of activation rows, in fp64 on the device.
 
@@ -54,16 +69,7 @@ class ActivationStatistics:
         return self.n + (self.flush_rows if self._held is not None else 0) + self._fill
 
     def _rows(self, act):
-        if not isinstance(act, torch.Tensor) or not act.is_cuda or act.dtype != torch.float32:
-            raise TypeError("sivae_hip.fid: activations must be a float32 ROCm tensor (no CPU fallback)")
-        if act.dim() == 4:
-            if act.shape[2] != 1 or act.shape[3] != 1:  # fid_score.py:195-196
-                act = torch.nn.functional.adaptive_avg_pool2d(act, output_size=(1, 1))
-            act = act.reshape(act.shape[0], -1)
-        if act.dim() != 2 or act.shape[1] != self.dims:
-            raise ValueError("sivae_hip.fid: expected activations [b, %d], [b, %d, 1, 1] or [b, %d, h, w], got %s"
-                             % (self.dims, self.dims, self.dims, tuple(act.shape)))
-        return act
+        return activation_rows(act, self.dims)
 
     def _flush_held(self):
         if self._held is not None:

@@ -1377,6 +1377,161 @@ def fid_xty(x, y, symmetric=False):
     return out
 
 
+# ------------------------------------------------------------------- pairwise figures on the features (feat_pairs.hip)
+FEAT_MAX_K = 8
+
+
+def _feat_rows(who, *xs):
+    """each x: a 2-D float32 ROCm tensor [n >= 1, 1 <= d <= FID_MAX_DIMS] with unit column stride, all of one d
+    -> (pointer, row stride, n) per tensor, then d"""
+    out = []
+    for x in xs:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError("sivae_hip.%s: tensor is on %s — the feature kernels need a ROCm device tensor and have "
+                               "no CPU fallback" % (who, getattr(x, "device", type(x).__name__)))
+        if x.dtype != torch.float32:
+            raise TypeError("sivae_hip.%s: expected float32 feature rows, got %s" % (who, x.dtype))
+        if x.dim() != 2 or x.shape[0] < 1 or not 1 <= x.shape[1] <= FID_MAX_DIMS or (x.shape[1] > 1 and x.stride(1) != 1) \
+                or x.shape[1] != xs[0].shape[1] or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+            raise ValueError("sivae_hip.%s: feature rows [n >= 1, 1 <= d <= %d] of one d with unit column stride, got %s "
+                             "with strides %s" % (who, FID_MAX_DIMS, tuple(x.shape), tuple(x.stride())))
+        out.append((_p(x), int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1]), int(x.shape[0])))
+    return out + [int(xs[0].shape[1])]
+
+
+def _feat_vec(who, t, n, dtype=torch.float64):
+    if not t.is_cuda:
+        raise RuntimeError("sivae_hip.%s: tensor is on %s — the feature kernels need a ROCm device tensor and have no "
+                           "CPU fallback" % (who, t.device))
+    if t.dtype != dtype or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError("sivae_hip.%s: expected a contiguous %s vector of %d elements, got %s %s"
+                         % (who, dtype, n, t.dtype, tuple(t.shape)))
+    return _p(t)
+
+
+def _feat_range(who, c0, c1, n):
+    c0, c1 = int(c0), int(n if c1 is None else c1)
+    if not 0 <= c0 <= c1 <= n:
+        raise ValueError("sivae_hip.%s: columns [%d, %d) of %d" % (who, c0, c1, n))
+    return c0, c1
+
+
+def feat_row_sqnorm(x):
+    """-> [n] fp64: the squared norm of every row of x (fp32 [n, d], unit column stride), summed in fp64, k ascending"""
+    (px, ldx, n), d = _feat_rows("feat_row_sqnorm", x)
+    out = torch.empty(n, dtype=torch.float64, device=x.device)
+    _lib.call("sivae_feat_row_sqnorm", px, ldx, n, d, _p(out), _s(x))
+    return out
+
+
+def feat_sqdist(x, nrmx, y, nrmy):
+    """-> D [nx, ny] fp64, D[i][j] = max(0, |x_i|^2 + |y_j|^2 - 2 x_i . y_j) with the norms of feat_row_sqnorm"""
+    (px, ldx, nx), (py, ldy, ny), d = _feat_rows("feat_sqdist", x, y)
+    pnx, pny = _feat_vec("feat_sqdist", nrmx, nx), _feat_vec("feat_sqdist", nrmy, ny)
+    out = torch.empty((nx, ny), dtype=torch.float64, device=x.device)
+    t0 = timer_begin()
+    _lib.call("sivae_feat_sqdist", px, ldx, nx, pnx, py, ldy, ny, pny, d, _p(out), ny, _s(x))
+    if t0 is not None:
+        timer_end(t0, "feat_sqdist", 2.0 * nx * ny * d)
+    return out
+
+
+def feat_knn_state(n, k, device):
+    """-> best [n, k] fp64, every entry +inf: the running state of feat_knn_update"""
+    if not 1 <= int(k) <= FEAT_MAX_K:
+        raise ValueError("sivae_hip.feat_knn_state: k must be in 1 .. %d, got %d" % (FEAT_MAX_K, k))
+    best = torch.empty((int(n), int(k)), dtype=torch.float64, device=device)
+    best.fill_(float("inf"))
+    return best
+
+
+def feat_knn_update(x, nrmx, y, nrmy, best, c0=0, c1=None, self_pairs=False):
+    """best [nx, k] (ascending) <- per row the k smallest of its values and the squared distances to the rows
+    y[c0:c1]; self_pairs: the pair j == i is left out by index (x and y are the same set).  In place."""
+    (px, ldx, nx), (py, ldy, ny), d = _feat_rows("feat_knn_update", x, y)
+    pnx, pny = _feat_vec("feat_knn_update", nrmx, nx), _feat_vec("feat_knn_update", nrmy, ny)
+    _require_f64("feat_knn_update", best)
+    if best.dim() != 2 or best.shape[0] != nx or not 1 <= best.shape[1] <= FEAT_MAX_K or not best.is_contiguous():
+        raise ValueError("sivae_hip.feat_knn_update: best must be contiguous [%d, 1 .. %d], got %s"
+                         % (nx, FEAT_MAX_K, tuple(best.shape)))
+    c0, c1 = _feat_range("feat_knn_update", c0, c1, ny)
+    t0 = timer_begin()
+    _lib.call("sivae_feat_knn_update", px, ldx, nx, pnx, py, ldy, ny, pny, c0, c1, d, int(best.shape[1]),
+              int(bool(self_pairs)), _p(best), _s(x))
+    if t0 is not None:
+        timer_end(t0, "feat_knn_update", 2.0 * nx * (c1 - c0) * d)
+
+
+def feat_within_state(n, device):
+    """-> count [n] int32, zero: the running state of feat_within_update"""
+    return torch.zeros(int(n), dtype=torch.int32, device=device)
+
+
+def feat_within_update(q, nrmq, x, nrmx, radius, count, c0=0, c1=None):
+    """count[j] += the number of rows i in [c0, c1) of x with sqdist(q_j, x_i) <= radius[i].  In place."""
+    (pq, ldq, nq), (px, ldx, nx), d = _feat_rows("feat_within_update", q, x)
+    pnq, pnx = _feat_vec("feat_within_update", nrmq, nq), _feat_vec("feat_within_update", nrmx, nx)
+    prad = _feat_vec("feat_within_update", radius, nx)
+    pcount = _feat_vec("feat_within_update", count, nq, torch.int32)
+    c0, c1 = _feat_range("feat_within_update", c0, c1, nx)
+    t0 = timer_begin()
+    _lib.call("sivae_feat_within_update", pq, ldq, nq, pnq, px, ldx, nx, pnx, prad, c0, c1, d, pcount, _s(q))
+    if t0 is not None:
+        timer_end(t0, "feat_within_update", 2.0 * nq * (c1 - c0) * d)
+
+
+def feat_poly_sums(x, y, gamma, coef0=1.0, degree=3, skip_diag=False):
+    """-> [S] fp64: per subset s the sum over i, j (i != j with skip_diag) of (gamma x[s, i] . y[s, j] + coef0)^degree;
+    x [S, m, d], y [S, n, d] fp32 with unit column stride"""
+    for t in (x, y):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("sivae_hip.feat_poly_sums: tensor is on %s — the feature kernels need a ROCm device "
+                               "tensor and have no CPU fallback" % getattr(t, "device", type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("sivae_hip.feat_poly_sums: expected float32 feature rows, got %s" % t.dtype)
+        if t.dim() != 3 or min(t.shape) < 1 or not t.shape[2] <= FID_MAX_DIMS or (t.shape[2] > 1 and t.stride(2) != 1) \
+                or (t.shape[1] > 1 and t.stride(1) < t.shape[2]) or t.stride(0) < 0:
+            raise ValueError("sivae_hip.feat_poly_sums: subsets [S, rows, 1 <= d <= %d] with unit column stride, got %s "
+                             "with strides %s" % (FID_MAX_DIMS, tuple(t.shape), tuple(t.stride())))
+    if x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+        raise ValueError("sivae_hip.feat_poly_sums: x %s and y %s differ in subsets or d" % (tuple(x.shape), tuple(y.shape)))
+    if int(degree) not in (1, 2, 3, 4):
+        raise ValueError("sivae_hip.feat_poly_sums: degree must be 1 .. 4, got %r" % (degree,))
+    S, m, d = x.shape
+    n = y.shape[1]
+    ldx, ldy = int(x.stride(1)) if m > 1 else d, int(y.stride(1)) if n > 1 else d
+    out = torch.empty(S, dtype=torch.float64, device=x.device)
+    nbytes = _lib.load().sivae_feat_poly_workspace_bytes(S, m)
+    ws = workspace(nbytes, x.device)
+    t0 = timer_begin()
+    _lib.call("sivae_feat_poly_sums", _p(x), int(x.stride(0)) if S > 1 else 0, ldx, _p(y), int(y.stride(0)) if S > 1 else 0,
+              ldy, S, m, n, d, float(gamma), float(coef0), int(degree), int(bool(skip_diag)), _p(out), _p(ws), ws.numel(),
+              _s(x))
+    if t0 is not None:
+        timer_end(t0, "feat_poly_sums", 2.0 * S * m * n * d)
+    return out
+
+
+def feat_gather(rows, index):
+    """-> [S, m, d] fp32: rows[index] for index int64 [S, m] on the device (plumbing: torch's gather into a buffer of this
+    module)"""
+    if not rows.is_cuda or not index.is_cuda:
+        raise RuntimeError("sivae_hip.feat_gather: tensor is on the CPU — the feature kernels need ROCm device tensors "
+                           "and have no CPU fallback")
+    if rows.dtype != torch.float32 or rows.dim() != 2 or index.dtype != torch.int64 or index.dim() != 2:
+        raise TypeError("sivae_hip.feat_gather: float32 rows [n, d] and int64 index [S, m]")
+    out = torch.empty((index.shape[0], index.shape[1], rows.shape[1]), dtype=torch.float32, device=rows.device)
+    torch.index_select(rows, 0, index.reshape(-1), out=out.view(-1, rows.shape[1]))
+    return out
+
+
+def feat_bank(capacity, d, device):
+    """-> a [capacity, d] fp32 buffer for feature rows (sivae_hip.fidelity.FeatureBank holds one)"""
+    if not 1 <= int(d) <= FID_MAX_DIMS:
+        raise ValueError("sivae_hip.feat_bank: dims must be in 1 .. %d, got %d" % (FID_MAX_DIMS, d))
+    return torch.empty((int(capacity), int(d)), dtype=torch.float32, device=device)
+
+
 class _SwitchWatch(type(sys)):
     """this module's type: assigning any of its attributes (ops.WINO4 = False, monkeypatch.setattr(ops, ...), dp's
     ops.SYNC_BN = sync) forgets the memoised routes"""

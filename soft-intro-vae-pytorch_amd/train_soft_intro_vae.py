@@ -192,6 +192,9 @@ def _require_device(device, local_rank=None):
 # metrics.fid_score pass, unchanged (host-side activation store, np.cov, scipy's sqrtm).
 # SIVAE_FID_CACHE_REAL=1 (default 0): the real-side statistics of the first pass serve the later passes.  The reference
 # recomputes them every pass on whatever 50 000 images its shuffled loader yields first, hence off by default.
+# SIVAE_FID_EXTRA=1 (default 0, device mode only): the same pass also keeps the feature rows and prints precision /
+# recall, density / coverage and KID (sivae_hip.fidelity) on one line; the FID value and everything done with it are
+# unchanged.
 FID_ARGS = dict(dims=2048, num_images=50000)  # what the reference's call passes (:287-288)
 FID_INCEPTION = None  # a feature network instead of the reference's InceptionV3 (a module whose call returns [features])
 
@@ -208,6 +211,18 @@ def _calculate_fid(loader, model, batch_size, device, real_stats):
     dims, num_images = FID_ARGS["dims"], FID_ARGS["num_images"]
     inception = FID_INCEPTION if FID_INCEPTION is not None else _fid.reference_inception(dims)
     inception.to(device)
+    if os.environ.get("SIVAE_FID_EXTRA", "0") == "1":
+        from sivae_hip import fidelity as _fidelity
+        real = real_stats.get("features")
+        if real is None:
+            real = _fidelity.real_features(loader, inception, dims, device, num_images)
+            if os.environ.get("SIVAE_FID_CACHE_REAL", "0") == "1":
+                real_stats["features"] = real
+        out = _fidelity.calculate_fidelity_given_dataset(loader, model, batch_size, cuda=True, dims=dims, device=device,
+                                                         num_images=num_images, inception=inception, real=real)
+        print("fidelity: precision %.6f recall %.6f density %.6f coverage %.6f kid %.6g +- %.6g"
+              % (out["precision"], out["recall"], out["density"], out["coverage"], out["kid_mean"], out["kid_std"]))
+        return out["fid"]
     stats = real_stats.get("stats")
     if stats is None:
         stats = _fid.real_statistics(loader, inception, dims, device, num_images)
