@@ -31,6 +31,8 @@ static inline int next_pow2(int v) {
   return p;
 }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// p is not a multiple of a (a power of two) bytes
+static inline bool sivae_misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
 // Tile geometry shared by the implicit-GEMM conv kernels: a pixel tile is TB images x TH rows x TW
 // cols (all powers of two, TB > 1 only when one tile covers a whole image).

@@ -1299,11 +1299,18 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999
 FID_MAX_DIMS = 8192
 
 
+def _require_device(who, kernels, *tensors, need="a ROCm device tensor", on=None):
+    """the FID and feature wrappers' one refusal of anything that is not on the device (`on`: said instead of where the
+    offending tensor is)"""
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("sivae_hip.%s: tensor is on %s — the %s kernels need %s and have no CPU fallback"
+                               % (who, on or getattr(t, "device", type(t).__name__), kernels, need))
+
+
 def _require_f64(who, *tensors):
     for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("sivae_hip.%s: tensor is on %s — the FID kernels need a ROCm device tensor and have no "
-                               "CPU fallback" % (who, t.device))
+        _require_device(who, "FID", t)
         if t.dtype != torch.float64:
             raise TypeError("sivae_hip.%s: expected float64, got %s" % (who, t.dtype))
 
@@ -1386,9 +1393,7 @@ def _feat_rows(who, *xs):
     -> (pointer, row stride, n) per tensor, then d"""
     out = []
     for x in xs:
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError("sivae_hip.%s: tensor is on %s — the feature kernels need a ROCm device tensor and have "
-                               "no CPU fallback" % (who, getattr(x, "device", type(x).__name__)))
+        _require_device(who, "feature", x)
         if x.dtype != torch.float32:
             raise TypeError("sivae_hip.%s: expected float32 feature rows, got %s" % (who, x.dtype))
         if x.dim() != 2 or x.shape[0] < 1 or not 1 <= x.shape[1] <= FID_MAX_DIMS or (x.shape[1] > 1 and x.stride(1) != 1) \
@@ -1400,9 +1405,7 @@ def _feat_rows(who, *xs):
 
 
 def _feat_vec(who, t, n, dtype=torch.float64):
-    if not t.is_cuda:
-        raise RuntimeError("sivae_hip.%s: tensor is on %s — the feature kernels need a ROCm device tensor and have no "
-                           "CPU fallback" % (who, t.device))
+    _require_device(who, "feature", t)
     if t.dtype != dtype or tuple(t.shape) != (n,) or not t.is_contiguous():
         raise ValueError("sivae_hip.%s: expected a contiguous %s vector of %d elements, got %s %s"
                          % (who, dtype, n, t.dtype, tuple(t.shape)))
@@ -1484,9 +1487,7 @@ def feat_poly_sums(x, y, gamma, coef0=1.0, degree=3, skip_diag=False):
     """-> [S] fp64: per subset s the sum over i, j (i != j with skip_diag) of (gamma x[s, i] . y[s, j] + coef0)^degree;
     x [S, m, d], y [S, n, d] fp32 with unit column stride"""
     for t in (x, y):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("sivae_hip.feat_poly_sums: tensor is on %s — the feature kernels need a ROCm device "
-                               "tensor and have no CPU fallback" % getattr(t, "device", type(t).__name__))
+        _require_device("feat_poly_sums", "feature", t)
         if t.dtype != torch.float32:
             raise TypeError("sivae_hip.feat_poly_sums: expected float32 feature rows, got %s" % t.dtype)
         if t.dim() != 3 or min(t.shape) < 1 or not t.shape[2] <= FID_MAX_DIMS or (t.shape[2] > 1 and t.stride(2) != 1) \
@@ -1515,9 +1516,7 @@ def feat_poly_sums(x, y, gamma, coef0=1.0, degree=3, skip_diag=False):
 def feat_gather(rows, index):
     """-> [S, m, d] fp32: rows[index] for index int64 [S, m] on the device (plumbing: torch's gather into a buffer of this
     module)"""
-    if not rows.is_cuda or not index.is_cuda:
-        raise RuntimeError("sivae_hip.feat_gather: tensor is on the CPU — the feature kernels need ROCm device tensors "
-                           "and have no CPU fallback")
+    _require_device("feat_gather", "feature", rows, index, need="ROCm device tensors", on="the CPU")
     if rows.dtype != torch.float32 or rows.dim() != 2 or index.dtype != torch.int64 or index.dim() != 2:
         raise TypeError("sivae_hip.feat_gather: float32 rows [n, d] and int64 index [S, m]")
     out = torch.empty((index.shape[0], index.shape[1], rows.shape[1]), dtype=torch.float32, device=rows.device)

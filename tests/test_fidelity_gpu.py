@@ -248,6 +248,25 @@ def test_poly_sums_degrees_and_coefficients():
         ops.feat_poly_sums(_dev(x), _dev(y), 0.1, 1.0, 5)
 
 
+@pytest.mark.parametrize("d", [1, 16, 67, 130])
+def test_both_orientations_are_one_tile_body(d):
+    """x . y through the rows operand (feat_poly_sums: X Y^T of one row each, gamma 1, coef0 0, degree 1) and through the
+    columns operand (fid_xty: X^T Y of one column each) is the same k-ascending fp64 MFMA accumulation of exact products
+    (csrc/f64_tile.h), and everything the poly epilogue adds to it is zero: the two results are equal bit for bit.
+    d: below a k-step, exactly one staged chunk, a ragged last chunk, several chunks with a ragged tail."""
+    from sivae_hip import ops
+    g = np.random.default_rng(4099 + d)
+    x = _dev((1.7 * g.standard_normal(d)).astype(np.float32))
+    y = _dev((0.6 * g.standard_normal(d) + 0.1).astype(np.float32))
+    if d > 1:  # mixed signs in both vectors and in the products
+        assert (x.min() < 0 < x.max()) and (y.min() < 0 < y.max()) and ((x * y).min() < 0 < (x * y).max())
+    rows = ops.feat_poly_sums(x[None, None], y[None, None], gamma=1.0, coef0=0.0, degree=1)
+    cols = ops.fid_xty(x.double()[:, None], y.double()[:, None])
+    assert tuple(rows.shape) == (1,) and tuple(cols.shape) == (1, 1) and rows.dtype == cols.dtype == torch.float64
+    print("d %d: rows %r, columns %r" % (d, float(rows[0]), float(cols[0, 0])))
+    assert float(rows[0]) != 0.0 and torch.equal(rows.view(1, 1), cols)
+
+
 def test_kid_against_the_oracle(monkeypatch):
     from sivae_hip import fidelity as FD
     real, fake = _sets(*RECORDED)
