@@ -7,6 +7,7 @@ soft_intro_vae_bootstrap/train_soft_intro_vae_bootstrap.py:44-246) so checkpoint
 parameter/buffer containers (they give the reference's default initialisation and key names) — their
 forward() is never called; Encoder/Decoder/ResidualBlock.forward dispatch to the HIP blocks.
 """
+import collections
 import os
 import sys
 
@@ -40,15 +41,18 @@ class ResidualBlock(nn.Module):
         self.bn2 = nn.BatchNorm2d(outc)
         self.relu2 = nn.LeakyReLU(0.2, inplace=True)
 
+    def _weights(self):
+        """the block's weights in the order functional.ResBlockFn takes them (its replay-cache tag is built from them)"""
+        return (None if self.conv_expand is None else self.conv_expand.weight, self.conv1.weight, self.bn1.weight,
+                self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias)
+
     def forward(self, x, post=None, cache=None, x_up=False, nseg=1, seg_rev=False, replay_update=True):
         """post in {None, 'pool', 'up', 'up_deferred'} fuses the AvgPool2d / Upsample that follows the block in the
         nets ('up_deferred': the next block reads this block's output through upsample addressing, x_up=True there).
         cache: see functional.ResBlockFn (activation cache for replaying an identical forward pass).
         A blocked bf16 input (bf16 mode, `set_compute_dtype`) runs the bf16 twin of the block.
         nseg > 1: x is a SEGMENTED batch (nseg passes laid end to end, per-pass BatchNorm statistics — functional.py)."""
-        args = (x, None if self.conv_expand is None else self.conv_expand.weight, self.conv1.weight, self.bn1.weight,
-                self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias, SF.BNState(self.bn1),
-                SF.BNState(self.bn2), post, cache, x_up)
+        args = (x, *self._weights(), SF.BNState(self.bn1), SF.BNState(self.bn2), post, cache, x_up)
         if x.dtype == torch.bfloat16:
             return SF16.residual_block(*args, nseg, seg_rev, replay_update)
         return SF.residual_block(*args, nseg, seg_rev, replay_update)
@@ -66,16 +70,6 @@ def set_compute_dtype(module, dtype):
     return module
 
 
-def _block_weights(m):
-    """the weight tuple a block's replay-cache tag is built from (same order as functional.ResBlockFn / ConvBiasFn)"""
-    if isinstance(m, ResidualBlock):
-        return (None if m.conv_expand is None else m.conv_expand.weight, m.conv1.weight, m.bn1.weight, m.bn1.bias,
-                m.conv2.weight, m.bn2.weight, m.bn2.bias)
-    if isinstance(m, nn.Conv2d):
-        return (m.weight, m.bias)
-    return ()
-
-
 def segments_supported(image_size, seg_images, compute_dtype="fp32"):
     """can `nseg` passes of seg_images images each run as ONE segmented batch through these networks?  (power-of-two
     maps, and no row of conv-epilogue statistics may straddle two passes: fp32 — a pass must be a whole number of the
@@ -88,55 +82,91 @@ def segments_supported(image_size, seg_images, compute_dtype="fp32"):
             and seg_images % 4 == 0 and SF.ops.SYNC_BN is None)
 
 
+# One layer group of a reference-shaped nn.Sequential, as `_run_main` dispatches it:
+#   kind         "stem" (conv5x5 -> BatchNorm -> LeakyReLU -> AvgPool2d), "block" (a ResidualBlock with the AvgPool2d /
+#                Upsample that follows it) or "predict" (a conv with bias)
+#   index        position in the Sequential of the group's first module: the group's slot in a replay cache
+#   block        the ResidualBlock ("block");  conv, bn: the Conv2d and its BatchNorm2d ("stem"), the Conv2d ("predict")
+#   post         None, "pool", "up" or "up_deferred" (ResidualBlock.forward; the stem's own AvgPool2d is "pool")
+#   x_up         the group reads its input through upsample addressing (the block before it deferred its Upsample)
+#   Ci, Cm, Co   channels in / between the block's two 3x3 convs (blocks only) / out
+#   H, W         the group's own resolution (with x_up: twice the stored input);  Ho, Wo: the stored output
+Step = collections.namedtuple("Step", "kind index block conv bn post x_up Ci Cm Co H W Ho Wo")
+
+
+def _plan(mods, H, W):
+    steps = []
+    i, n = 0, len(mods)
+    x_up = False  # the running map stands for Upsample(2,'nearest') of what is stored
+    while i < n:
+        m = mods[i]
+        nxt = mods[i + 1] if i + 1 < n else None
+        if isinstance(m, ResidualBlock):
+            post, Ho, Wo = None, H, W
+            if isinstance(nxt, nn.AvgPool2d):
+                post, Ho, Wo = "pool", H // 2, W // 2
+            elif isinstance(nxt, nn.Upsample):
+                # leave the Upsample to the next block when that is a ResidualBlock (its kernels read through
+                # h>>1, w>>1; the residual add needs the upsampled width to be a multiple of 4)
+                defer = DEFER_UPSAMPLE and i + 2 < n and isinstance(mods[i + 2], ResidualBlock) and W % 2 == 0
+                post, Ho, Wo = ("up_deferred", H, W) if defer else ("up", 2 * H, 2 * W)
+            steps.append(Step("block", i, m, None, None, post, x_up, m.conv1.in_channels, m.conv1.out_channels,
+                              m.conv2.out_channels, H, W, Ho, Wo))
+            x_up = post == "up_deferred"
+            H, W = (2 * Ho, 2 * Wo) if x_up else (Ho, Wo)
+            i += 1 if post is None else 2
+        elif isinstance(m, nn.Conv2d) and isinstance(nxt, nn.BatchNorm2d):
+            # encoder stem: conv5x5 -> BN -> LeakyReLU -> AvgPool2d
+            assert isinstance(mods[i + 2], nn.LeakyReLU) and isinstance(mods[i + 3], nn.AvgPool2d)
+            steps.append(Step("stem", i, None, m, nxt, "pool", False, m.in_channels, None, m.out_channels, H, W,
+                              H // 2, W // 2))
+            H, W = H // 2, W // 2
+            i += 4
+        elif isinstance(m, nn.Conv2d):
+            steps.append(Step("predict", i, None, m, None, None, False, m.in_channels, None, m.out_channels, H, W, H, W))
+            i += 1
+        else:
+            raise RuntimeError("sivae_hip: unexpected layer %s in network" % type(m).__name__)
+    return tuple(steps)
+
+
+def main_plan(main, size):
+    """The layer groups of a reference-shaped nn.Sequential fed an (H, W) map: a tuple of `Step`.  It follows from the
+    Sequential's structure, the map size and DEFER_UPSAMPLE alone, and is kept ON the Sequential under all three
+    (like functional._cached_pack keeps packs on the parameter: it dies with the model), so a forward pass parses
+    nothing, and a Sequential whose layers were edited since is planned anew."""
+    plans = main.__dict__.setdefault("_sivae_plans", {})
+    key = (size[0], size[1], DEFER_UPSAMPLE, *main._modules.values())
+    plan = plans.get(key)
+    if plan is None:
+        plan = plans[key] = _plan(key[3:], size[0], size[1])
+    return plan
+
+
 def _run_main(main, x, cache=None, bf16=None, nseg=1, seg_rev=False, replay_update=True):
-    """Walk a reference-shaped nn.Sequential, dispatching each group of layers to its fused HIP block.
+    """Run a reference-shaped nn.Sequential: each layer group of its `main_plan` goes to its fused HIP block.
     x: fp32 NCHW, or a blocked bf16 activation (bf16 mode): the blocks dispatch on the input dtype unless `bf16` says
     otherwise (the bf16 encoder hands its stem the fp32 image)."""
     if bf16 is None:
         bf16 = x.dtype == torch.bfloat16
     F_ = SF16 if bf16 else SF
-    mods = list(main.children())
-    i, n = 0, len(mods)
-    x_up = False  # x currently stands for Upsample(2,'nearest')(x): the consumers read it through upsample addressing
     stale = False  # an earlier block of this pass missed its replay cache
-    while i < n:
-        m = mods[i]
-        nxt = mods[i + 1] if i + 1 < n else None
-        sub = None if cache is None else cache.setdefault(i, {})
+    for s in main_plan(main, (x.shape[2], x.shape[3])):  # (dims 2, 3 are H, W in both layouts)
+        sub = None if cache is None else cache.setdefault(s.index, {})
         if sub is not None and sub.get("y") is not None:
             # a cached block is replayed only if its own weights are unchanged AND every block before it was replayed
-            # too (a recomputed block hands its successors a new input)
-            if stale or sub.get("tag") != SF.cache_tag(_block_weights(m)):
+            # too (a recomputed block hands its successors a new input); the tag is built from the weights in the order
+            # functional.ResBlockFn / ConvBiasFn take them (the stem has no cache: its slot never holds a "y")
+            weights = s.block._weights() if s.kind == "block" else (s.conv.weight, s.conv.bias)
+            if stale or sub.get("tag") != SF.cache_tag(weights):
                 sub.clear()
                 stale = True
-        if isinstance(m, ResidualBlock):
-            if isinstance(nxt, nn.AvgPool2d):
-                x = m(x, post="pool", cache=sub, x_up=x_up, nseg=nseg, seg_rev=seg_rev, replay_update=replay_update)
-                x_up = False
-                i += 2
-            elif isinstance(nxt, nn.Upsample):
-                # leave the Upsample to the next block when that is a ResidualBlock (its kernels read through
-                # h>>1, w>>1; the residual add needs the upsampled width to be a multiple of 4)
-                w_here = x.shape[3] * (2 if x_up else 1)  # (dim 3 is W in both layouts)
-                defer = DEFER_UPSAMPLE and i + 2 < n and isinstance(mods[i + 2], ResidualBlock) and w_here % 2 == 0
-                x = m(x, post="up_deferred" if defer else "up", cache=sub, x_up=x_up, nseg=nseg, seg_rev=seg_rev,
-                      replay_update=replay_update)
-                x_up = defer
-                i += 2
-            else:
-                x = m(x, cache=sub, x_up=x_up, nseg=nseg, seg_rev=seg_rev, replay_update=replay_update)
-                x_up = False
-                i += 1
-        elif isinstance(m, nn.Conv2d) and isinstance(nxt, nn.BatchNorm2d):
-            # encoder stem: conv5x5 -> BN -> LeakyReLU -> AvgPool2d
-            assert isinstance(mods[i + 2], nn.LeakyReLU) and isinstance(mods[i + 3], nn.AvgPool2d)
-            x = F_.stem(x, m.weight, nxt.weight, nxt.bias, SF.BNState(nxt), nseg, seg_rev)
-            i += 4
-        elif isinstance(m, nn.Conv2d):
-            x = F_.conv_bias(x, m.weight, m.bias, sub)
-            i += 1
+        if s.kind == "block":
+            x = s.block(x, post=s.post, cache=sub, x_up=s.x_up, nseg=nseg, seg_rev=seg_rev, replay_update=replay_update)
+        elif s.kind == "stem":
+            x = F_.stem(x, s.conv.weight, s.bn.weight, s.bn.bias, SF.BNState(s.bn), nseg, seg_rev)
         else:
-            raise RuntimeError("sivae_hip: unexpected layer %s in network" % type(m).__name__)
+            x = F_.conv_bias(x, s.conv.weight, s.conv.bias, sub)
     return x
 
 
@@ -266,5 +296,6 @@ class Decoder(nn.Module):
         return _run_main(self.main, y, cache, nseg=nseg, seg_rev=seg_rev, replay_update=replay_update)
 
 
-# (assigning a switch of this module forgets the memoised routes and block plans, like a switch of `ops` does)
+# (assigning a switch of this module forgets the memoised routes and block plans, like a switch of `ops` does; the
+# network plans are kept under DEFER_UPSAMPLE's value)
 sys.modules[__name__].__class__ = SF.ops._SwitchWatch

@@ -220,50 +220,29 @@ def block_route(B, nseg, Ci, Cm, Co, H, W, x_up, post, bn_fused=True, pool_dgrad
 
 
 def walk_routes(channels, image_size, B, nseg=1, cdim=3, convs=None):
-    """the route class of every layer group nn._run_main dispatches for the bf16 Encoder and Decoder at batch B (nseg > 1:
-    a segmented batch of B images) — by walking _run_main itself on meta tensors with the block / stem / predict entry
-    points replaced by recorders (nothing runs).  convs (a list): gets (Ci, Co, H, W, ks code) of every conv whose
-    epilogue writes BatchNorm statistics (the stem's and both 3x3 convs of every block)"""
+    """the route class of every layer group of the bf16 Encoder and Decoder at batch B (nseg > 1: a segmented batch of B
+    images), in the order of nn.main_plan (the networks are built on the meta device; nothing runs).  convs (a list):
+    gets (Ci, Co, H, W, ks code) of every conv whose epilogue writes BatchNorm statistics (the stem's and both 3x3 convs
+    of every block)"""
     from sivae_hip import nn as N
     from sivae_hip import functional16 as SF16
     from sivae_hip import ops16
+    with torch.device("meta"):
+        enc = N.Encoder(cdim, 8, channels, image_size)
+        dec = N.Decoder(cdim, 8, channels, image_size, conv_input_size=enc.conv_output_size)
     rec = []
-
-    def blk(self, x, post=None, cache=None, x_up=False, nseg=1, seg_rev=False, replay_update=True):
-        Bx, _, Hs, Ws, _ = x.shape
-        H, W = (2 * Hs, 2 * Ws) if x_up else (Hs, Ws)
-        Ci, Cm, Co = self.conv1.in_channels, self.conv1.out_channels, self.conv2.out_channels
-        rec.append(block_route(Bx, nseg, Ci, Cm, Co, H, W, x_up, post))
-        if convs is not None:
-            convs.extend([(Ci, Cm, H, W, 3), (Cm, Co, H, W, 3)])
-        Ho, Wo = (H // 2, W // 2) if post == "pool" else ((2 * H, 2 * W) if post == "up" else (H, W))
-        return torch.empty(Bx, ops16.cblocks(Co), Ho, Wo, 8, dtype=torch.bfloat16, device="meta")
-
-    def stem(x, w, g, b, st, nseg=1, seg_rev=False):
-        kw = SF16._kwpack_ok(w, w.shape[1])
-        rec.append(("stem", kw, nseg > 1))
-        if convs is not None:
-            convs.append((5 * w.shape[1] if kw else w.shape[1], w.shape[0], x.shape[2], x.shape[3],
-                          ops16.KS51 if kw else w.shape[2]))
-        return torch.empty(x.shape[0], ops16.cblocks(w.shape[0]), x.shape[2] // 2, x.shape[3] // 2, 8,
-                           dtype=torch.bfloat16, device="meta")
-
-    def conv_bias(x, w, bias, cache=None):
-        rec.append(("predict", SF16._kwpack_ok(w, w.shape[0]), bias is not None))
-        return x
-
-    orig = (N.ResidualBlock.forward, SF16.stem, SF16.conv_bias)
-    try:
-        N.ResidualBlock.forward, SF16.stem, SF16.conv_bias = blk, stem, conv_bias
-        with torch.device("meta"):
-            enc = N.Encoder(cdim, 8, channels, image_size)
-            dec = N.Decoder(cdim, 8, channels, image_size, conv_input_size=enc.conv_output_size)
-        N._run_main(enc.main, torch.empty(B, cdim, image_size, image_size, device="meta"), bf16=True, nseg=nseg)
-        C, Hs, Ws = enc.conv_output_size
-        N._run_main(dec.main, torch.empty(B, ops16.cblocks(C), Hs, Ws, 8, dtype=torch.bfloat16, device="meta"),
-                    nseg=nseg)
-    finally:
-        N.ResidualBlock.forward, SF16.stem, SF16.conv_bias = orig
+    for s in N.main_plan(enc.main, (image_size, image_size)) + N.main_plan(dec.main, enc.conv_output_size[1:]):
+        if s.kind == "block":
+            rec.append(block_route(B, nseg, s.Ci, s.Cm, s.Co, s.H, s.W, s.x_up, s.post))
+            if convs is not None:
+                convs.extend([(s.Ci, s.Cm, s.H, s.W, 3), (s.Cm, s.Co, s.H, s.W, 3)])
+        elif s.kind == "stem":
+            kw = SF16._kwpack_ok(s.conv.weight, s.Ci)
+            rec.append(("stem", kw, nseg > 1))
+            if convs is not None:
+                convs.append((5 * s.Ci if kw else s.Ci, s.Co, s.H, s.W, ops16.KS51 if kw else s.conv.kernel_size[0]))
+        else:
+            rec.append(("predict", SF16._kwpack_ok(s.conv.weight, s.Co), s.conv.bias is not None))
     return rec
 
 

@@ -439,57 +439,35 @@ def block_cases(ops, B, Ci, Cm, Co, H, W, x_up, post, nseg, has_exp):
 
 
 def network_cases(ops, channels, image_size, B, nseg=1, cdim=3):
-    """[(layer, kind, params)]: nn._run_main walked over the fp32 Encoder and Decoder on meta tensors with the block /
-    stem / predict entry points replaced by functions that list the ops-level calls they would make (nothing runs)"""
+    """[(layer, kind, params)]: the ops-level calls of every layer group of the fp32 Encoder and Decoder, in the order of
+    nn.main_plan (the networks are built on the meta device; nothing runs)"""
     from sivae_hip import functional as SF
     from sivae_hip import nn as N
+    with torch.device("meta"), contextlib.redirect_stdout(None):  # (the constructors print their shapes)
+        enc = N.Encoder(cdim, 8, channels, image_size)
+        dec = N.Decoder(cdim, 8, channels, image_size, conv_input_size=enc.conv_output_size)
     out = []
-    where = [""]
-
-    def blk(self, x, post=None, cache=None, x_up=False, nseg=1, seg_rev=False, replay_update=True):
-        Bx, Ci, H, W = x.shape
-        if x_up:
-            H, W = 2 * H, 2 * W
-        Cm, Co = self.conv1.out_channels, self.conv2.out_channels
-        layer = "%s.block%dx%d" % (where[0], H, W)
-        out.extend((layer, k, p) for k, p in block_cases(ops, Bx, Ci, Cm, Co, H, W, x_up, post, nseg,
-                                                         self.conv_expand is not None))
-        Ho, Wo = (H // 2, W // 2) if post == "pool" else ((2 * H, 2 * W) if post == "up" else (H, W))
-        return M(Bx, Co, Ho, Wo)
-
-    def stem(x, w, g, b, st, nseg=1, seg_rev=False):
-        Bx, Ci, H, W = x.shape
-        Co = w.shape[0]
-        out.append((where[0] + ".stem", "fwd", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=5, want_stats=True)))
-        out.append((where[0] + ".stem", "bn_bwd", dict(B=Bx, C=Co, H=H, W=W, act=2, dy_pooled=True, has_pg_out=True,
-                                                       nseg=nseg)))
-        if not SF.stem_edge5(w):
-            out.append((where[0] + ".stem", "wgrad", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=5, has_out=True)))
-        return M(Bx, Co, H // 2, W // 2)
-
-    def conv_bias(x, w, bias, cache=None):
-        Bx, Ci, H, W = x.shape
-        Co, ks = w.shape[0], w.shape[2]
-        edge_fwd, edge_wgrad = SF.predict_edge5(w)
-        if not edge_fwd:
-            out.append((where[0] + ".predict", "fwd", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=ks, bias=bias is not None)))
-        if not edge_wgrad:
-            out.append((where[0] + ".predict", "wgrad", dict(B=Bx, Ci=Ci, Co=Co, H=H, W=W, ks=ks, has_out=True)))
-        out.append((where[0] + ".predict", "fwd", dict(B=Bx, Ci=Co, Co=Ci, H=H, W=W, ks=ks, mode=1)))
-        return M(Bx, Co, H, W)
-
-    orig = (N.ResidualBlock.forward, SF.stem, SF.conv_bias)
-    try:
-        N.ResidualBlock.forward, SF.stem, SF.conv_bias = blk, stem, conv_bias
-        with torch.device("meta"), contextlib.redirect_stdout(None):  # (the constructors print their shapes)
-            enc = N.Encoder(cdim, 8, channels, image_size)
-            dec = N.Decoder(cdim, 8, channels, image_size, conv_input_size=enc.conv_output_size)
-        where[0] = "enc"
-        N._run_main(enc.main, M(B, cdim, image_size, image_size), nseg=nseg)
-        where[0] = "dec"
-        N._run_main(dec.main, M(B, *enc.conv_output_size), nseg=nseg)
-    finally:
-        N.ResidualBlock.forward, SF.stem, SF.conv_bias = orig
+    for where, main, size in (("enc", enc.main, (image_size, image_size)), ("dec", dec.main, enc.conv_output_size[1:])):
+        for s in N.main_plan(main, size):
+            d = dict(B=B, Ci=s.Ci, Co=s.Co, H=s.H, W=s.W)
+            if s.kind == "block":
+                layer = "%s.block%dx%d" % (where, s.H, s.W)
+                out.extend((layer, k, p) for k, p in block_cases(ops, B, s.Ci, s.Cm, s.Co, s.H, s.W, s.x_up, s.post,
+                                                                 nseg, s.block.conv_expand is not None))
+            elif s.kind == "stem":
+                out.append((where + ".stem", "fwd", dict(d, ks=5, want_stats=True)))
+                out.append((where + ".stem", "bn_bwd", dict(B=B, C=s.Co, H=s.H, W=s.W, act=2, dy_pooled=True,
+                                                            has_pg_out=True, nseg=nseg)))
+                if not SF.stem_edge5(s.conv.weight):
+                    out.append((where + ".stem", "wgrad", dict(d, ks=5, has_out=True)))
+            else:
+                ks = s.conv.kernel_size[0]
+                edge_fwd, edge_wgrad = SF.predict_edge5(s.conv.weight)
+                if not edge_fwd:
+                    out.append((where + ".predict", "fwd", dict(d, ks=ks, bias=s.conv.bias is not None)))
+                if not edge_wgrad:
+                    out.append((where + ".predict", "wgrad", dict(d, ks=ks, has_out=True)))
+                out.append((where + ".predict", "fwd", dict(d, Ci=s.Co, Co=s.Ci, ks=ks, mode=1)))
     return out
 
 

@@ -14,7 +14,7 @@ import block_checks16 as bc
 
 
 def test_every_benchmarked_bf16_route_has_a_block_referee():
-    """walks nn._run_main over the Encoder / Decoder of config 3 (128x128, batch 128), celeb256_bf16_bs128 and the
+    """reads nn.main_plan of the Encoder / Decoder of config 3 (128x128, batch 128), celeb256_bf16_bs128 and the
     16-image 256x256 shard, unpaired and as segmented pairs, and requires each route class to be the class of a
     block_checks16 case at that case's own (smaller) batch — the classes are asked of ops16's route functions in both
     places, so a dispatch change that opens a new route fails here until a case covers it"""
