@@ -903,6 +903,67 @@ int sivae_feat_poly_sums(const float* X, long long x_stride_s, long long ldx, co
                          long long ldy, int S, int m, int n, int d, double gamma, double coef0, int degree, int skip_diag,
                          double* out, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
 
+/* ---- the style variant's non-conv layers: fused instance-norm chains and the blur (style.hip) ------------------------
+ * What follows every 3x3 convolution of style_soft_intro_vae/net.py, one forward and one backward kernel per chain.
+ * float32, NCHW contiguous, any B, C >= 1 and any H, W with H W >= 2 (torch's InstanceNorm refuses a single element:
+ * SIVAE_ERR_SHAPE); SIVAE_ERR_RANGE for B C > 2^31 - 1 or H W > 2^30 - 1.  One block owns one (b, c) plane; planes up
+ * to 65536 elements (forward) / 16384 elements (backward) stay in registers between the statistics and the apply step
+ * (one read per direction), larger ones are read again.  Every pointer must be 4-byte aligned (SIVAE_ERR_SHAPE); where
+ * every plane is 16-byte aligned the kernels use 16-byte accesses, anywhere else guarded scalar ones over the SAME
+ * partition of the plane (an H W that is no multiple of 4 ends in a scalar tail), so the alignment changes no bit.
+ * No atomics.  Every sum runs in a fixed order (a thread's elements in index order in fp32; lanes, then waves, in fp64):
+ * two runs are bit-identical, and one plane's results depend neither on B, on C nor on the other planes.  Null
+ * pointers, shapes and modes are refused before any launch.
+ *
+ * sivae_style_dec_fwd replaces net.py:169-185 and :189-205 (DecodeBlock.forward: noise injection, bias,
+ * F.leaky_relu(x, 0.2), nn.InstanceNorm2d(affine=False), style_mod of net.py:32-34):
+ *   mode 1: noise [B][1][H][W],  u = x + noise_weight[c] noise[b][h][w]
+ *   mode 2: noise [1][1][H][W], the same plane for every sample (the reference's 'batch_constant')
+ *   mode 0: no noise tensor (noise and noise_weight may be NULL),  u = x + s k exp(-x^2 / (2 s^2)), k = 0.8 / sqrt(2 pi),
+ *           s = sqrt(layer + 1)  (layer >= 0)
+ *   t = lrelu_0.2(u + bias[c]);  per plane m = mean t, v = mean (t - m)^2, r = 1 / sqrt(v + eps), xh = (t - m) r
+ *   y = xh (style[b][c] + 1) + style[b][C + c]                                  (style [B][2 C])
+ * Outputs y [B][C][H][W], mean = m [B][C], rstd = r [B][C].  SIVAE_ERR_MODE for another mode; SIVAE_ERR_NULL for a
+ * missing x / bias / style / output, and for a missing noise or noise_weight in modes 1 and 2; SIVAE_ERR_SHAPE for a
+ * negative layer or eps. */
+int sivae_style_dec_fwd(const float* x, const float* noise, const float* noise_weight, const float* bias,
+                        const float* style, float* y, float* mean, float* rstd, int B, int C, int H, int W, int mode,
+                        int layer, float eps, sivae_stream_t stream);
+/* Its backward from dy and the forward's inputs, mean and rstd; t is recomputed, never stored.  With sums over a plane:
+ *   dstyle[b][C + c] = sum dy;   dstyle[b][c] = sum dy xh
+ *   dt = r (style[b][c] + 1) (dy - dstyle[b][C + c] / HW - xh dstyle[b][c] / HW)
+ *   dp = dt (t > 0 ? 1 : 0.2)                      (torch's LeakyReLU gradient: the slope 0.2 at 0)
+ *   dbias[c] = sum_{b, hw} dp;   dnoise_weight[c] = sum_{b, hw} dp noise   (modes 1, 2)
+ *   dx = dp (modes 1, 2);   dx = dp (1 - k (x / s) exp(-x^2 / (2 s^2)))   (mode 0)
+ * dx, dnoise_weight [C], dbias [C] and dstyle [B][2 C] may each be NULL: only what is asked for is computed (nothing is
+ * launched when all four are NULL); a dnoise_weight in mode 0 is SIVAE_ERR_MODE.  The sums over b run in ascending b in
+ * a second small launch, from per-plane fp64 partials in the workspace (2 B C doubles, 8-byte aligned), which is needed
+ * only when dbias or dnoise_weight is asked for: SIVAE_ERR_WORKSPACE then for a NULL or too small one. */
+size_t sivae_style_dec_bwd_workspace_bytes(int B, int C);
+int sivae_style_dec_bwd(const float* dy, const float* x, const float* noise, const float* noise_weight, const float* bias,
+                        const float* style, const float* mean, const float* rstd, float* dx, float* dnoise_weight,
+                        float* dbias, float* dstyle, int B, int C, int H, int W, int mode, int layer, void* workspace,
+                        size_t workspace_bytes, sivae_stream_t stream);
+/* sivae_style_enc_fwd replaces net.py:94-101 and :113-121 (EncodeBlock.forward: bias, F.leaky_relu(x, 0.2), the style
+ * statistics (mean, std), nn.InstanceNorm2d(affine=False)):
+ *   t = lrelu_0.2(x + bias[c]);  m = mean t, v = mean (t - m)^2;  std = sqrt(v) (no eps);  xn = (t - m) / sqrt(v + eps)
+ * Outputs xn [B][C][H][W], mean [B][C], std [B][C]; all three are differentiable. */
+int sivae_style_enc_fwd(const float* x, const float* bias, float* xn, float* mean, float* stddev, int B, int C, int H,
+                        int W, float eps, sivae_stream_t stream);
+/* Its backward from (dxn, dmean, dstd), each of which may be NULL (a zero gradient), with r = 1 / sqrt(std^2 + eps):
+ *   dt = r (dxn - mean dxn - xn mean(dxn xn)) + dmean / HW + dstd (t - m) / (HW std)
+ *   dp = dt (t > 0 ? 1 : 0.2);   dx = dp;   dbias[c] = sum_{b, hw} dp  (ascending b, as above; workspace: B C doubles)
+ * Where std == 0 (a constant plane) the reference's gradient is NaN (the square root's derivative at 0): this kernel
+ * DROPS the dstd term there, and every gradient stays finite.  dx and dbias may each be NULL. */
+size_t sivae_style_enc_bwd_workspace_bytes(int B, int C);
+int sivae_style_enc_bwd(const float* dxn, const float* dmean, const float* dstd, const float* x, const float* bias,
+                        const float* mean, const float* stddev, float* dx, float* dbias, int B, int C, int H, int W,
+                        float eps, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+/* The depthwise [1, 2, 1] x [1, 2, 1] / 16 filter with zero padding (net.py:49-60, Blur), y [B][C][H][W] from x, any
+ * H, W >= 1; y must not overlap x.  The filter is its own adjoint: the same call is the backward (dx from dy).  Rows
+ * first, (l + 2 c) + r, then (top + 2 mid) + bottom, times 1 / 16. */
+int sivae_style_blur(const float* x, float* y, int B, int C, int H, int W, sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

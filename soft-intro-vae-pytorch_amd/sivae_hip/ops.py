@@ -1531,6 +1531,126 @@ def feat_bank(capacity, d, device):
     return torch.empty((int(capacity), int(d)), dtype=torch.float32, device=device)
 
 
+# ------------------------------------------------------------------------------------------------ style variant (style.hip)
+STYLE_NOISE_NONE, STYLE_NOISE_PER_SAMPLE, STYLE_NOISE_BATCH_CONSTANT = 0, 1, 2
+
+
+def _style_f32(who, *tensors):
+    for t in tensors:
+        if t is None:
+            continue
+        _require_device(who, "style", t)
+        if t.dtype != torch.float32:
+            raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("sivae_hip.%s: tensor must be contiguous" % who)
+
+
+def _style_dims(who, x, bias, style=None, noise=None, noise_weight=None, mode=0):
+    if x.dim() != 4 or x.shape[2] * x.shape[3] < 2:
+        raise ValueError("sivae_hip.%s: expected x [B, C, H, W] with H W >= 2, got %s" % (who, tuple(x.shape)))
+    B, C, H, W = x.shape
+    if bias.numel() != C:
+        raise ValueError("sivae_hip.%s: bias must have C = %d elements, got %s" % (who, C, tuple(bias.shape)))
+    if style is not None and tuple(style.shape) != (B, 2 * C):
+        raise ValueError("sivae_hip.%s: style must be [B, 2 C] = (%d, %d), got %s" % (who, B, 2 * C, tuple(style.shape)))
+    if mode not in (STYLE_NOISE_NONE, STYLE_NOISE_PER_SAMPLE, STYLE_NOISE_BATCH_CONSTANT):
+        raise ValueError("sivae_hip.%s: noise mode must be 0, 1 or 2, got %r" % (who, mode))
+    if mode != STYLE_NOISE_NONE:
+        want = (B if mode == STYLE_NOISE_PER_SAMPLE else 1, 1, H, W)
+        if noise is None or noise_weight is None or tuple(noise.shape) != want or noise_weight.numel() != C:
+            raise ValueError("sivae_hip.%s: noise mode %d needs noise %s and noise_weight with C = %d elements"
+                             % (who, mode, want, C))
+    return B, C, H, W
+
+
+def style_dec_fwd(x, noise, noise_weight, bias, style, mode, layer=0, eps=1e-8):
+    """-> (y, mean [B, C], rstd [B, C]): noise injection (mode 1: noise [B, 1, H, W]; 2: [1, 1, H, W]; 0: none, the
+    layer's fixed bump) -> bias -> LeakyReLU(0.2) -> InstanceNorm -> y = xh (style[:, :C] + 1) + style[:, C:]"""
+    if mode == STYLE_NOISE_NONE:
+        noise = noise_weight = None
+    _style_f32("style_dec_fwd", x, noise, noise_weight, bias, style)
+    B, C, H, W = _style_dims("style_dec_fwd", x, bias, style, noise, noise_weight, mode)
+    y = torch.empty_like(x)
+    mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    t0 = timer_begin()
+    _lib.call("sivae_style_dec_fwd", _p(x), _p(noise), _p(noise_weight), _p(bias), _p(style), _p(y), _p(mean), _p(rstd),
+              B, C, H, W, int(mode), int(layer), float(eps), _s(x))
+    if t0 is not None:
+        timer_end(t0, "style_dec_fwd_kernel", 12.0 * x.numel())
+    return y, mean, rstd
+
+
+def style_dec_bwd(dy, x, noise, noise_weight, bias, style, mean, rstd, mode, layer=0, want_dx=True, want_dnw=True,
+                  want_dbias=True, want_dstyle=True):
+    """-> (dx, dnoise_weight [C], dbias [C], dstyle [B, 2 C]), None for what is not wanted (and for dnoise_weight in mode
+    0); the activation is recomputed from x"""
+    if mode == STYLE_NOISE_NONE:
+        noise = noise_weight = None
+        want_dnw = False
+    _style_f32("style_dec_bwd", dy, x, noise, noise_weight, bias, style, mean, rstd)
+    B, C, H, W = _style_dims("style_dec_bwd", x, bias, style, noise, noise_weight, mode)
+    if dy.shape != x.shape or tuple(mean.shape) != (B, C) or tuple(rstd.shape) != (B, C):
+        raise ValueError("sivae_hip.style_dec_bwd: dy like x and mean, rstd [B, C] expected")
+    dx = torch.empty_like(x) if want_dx else None
+    dnw = torch.empty(C, dtype=torch.float32, device=x.device) if want_dnw else None
+    dbias = torch.empty(C, dtype=torch.float32, device=x.device) if want_dbias else None
+    dstyle = torch.empty((B, 2 * C), dtype=torch.float32, device=x.device) if want_dstyle else None
+    ws = workspace(_lib.load().sivae_style_dec_bwd_workspace_bytes(B, C), x.device) if (want_dnw or want_dbias) else None
+    t0 = timer_begin()
+    _lib.call("sivae_style_dec_bwd", _p(dy), _p(x), _p(noise), _p(noise_weight), _p(bias), _p(style), _p(mean), _p(rstd),
+              _p(dx), _p(dnw), _p(dbias), _p(dstyle), B, C, H, W, int(mode), int(layer), _p(ws),
+              0 if ws is None else ws.numel(), _s(x))
+    if t0 is not None:
+        timer_end(t0, "style_dec_bwd_kernel", 30.0 * x.numel())
+    return dx, dnw, dbias, dstyle
+
+
+def style_enc_fwd(x, bias, eps=1e-5):
+    """-> (xn, mean [B, C], std [B, C]) of t = lrelu_0.2(x + bias): xn = (t - mean) / sqrt(var + eps), std = sqrt(var)"""
+    _style_f32("style_enc_fwd", x, bias)
+    B, C, H, W = _style_dims("style_enc_fwd", x, bias)
+    xn = torch.empty_like(x)
+    mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    std = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    t0 = timer_begin()
+    _lib.call("sivae_style_enc_fwd", _p(x), _p(bias), _p(xn), _p(mean), _p(std), B, C, H, W, float(eps), _s(x))
+    if t0 is not None:
+        timer_end(t0, "style_enc_fwd_kernel", 8.0 * x.numel())
+    return xn, mean, std
+
+
+def style_enc_bwd(dxn, dmean, dstd, x, bias, mean, std, eps=1e-5, want_dx=True, want_dbias=True):
+    """-> (dx, dbias [C]) from the three upstream gradients (each may be None: zero); where std == 0 the dstd term is
+    dropped (the reference's gradient is NaN there)"""
+    _style_f32("style_enc_bwd", dxn, dmean, dstd, x, bias, mean, std)
+    B, C, H, W = _style_dims("style_enc_bwd", x, bias)
+    if (dxn is not None and dxn.shape != x.shape) or any(t is not None and tuple(t.shape) != (B, C)
+                                                         for t in (dmean, dstd, mean, std)):
+        raise ValueError("sivae_hip.style_enc_bwd: dxn like x and dmean, dstd, mean, std [B, C] expected")
+    dx = torch.empty_like(x) if want_dx else None
+    dbias = torch.empty(C, dtype=torch.float32, device=x.device) if want_dbias else None
+    ws = workspace(_lib.load().sivae_style_enc_bwd_workspace_bytes(B, C), x.device) if want_dbias else None
+    t0 = timer_begin()
+    _lib.call("sivae_style_enc_bwd", _p(dxn), _p(dmean), _p(dstd), _p(x), _p(bias), _p(mean), _p(std), _p(dx), _p(dbias),
+              B, C, H, W, float(eps), _p(ws), 0 if ws is None else ws.numel(), _s(x))
+    if t0 is not None:
+        timer_end(t0, "style_enc_bwd_kernel", 20.0 * x.numel())
+    return dx, dbias
+
+
+def style_blur(x):
+    """the depthwise [1, 2, 1] x [1, 2, 1] / 16 filter with zero padding; its own adjoint (the backward is the same call)"""
+    _style_f32("style_blur", x)
+    if x.dim() != 4:
+        raise ValueError("sivae_hip.style_blur: expected x [B, C, H, W], got %s" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    y = torch.empty_like(x)
+    _lib.call("sivae_style_blur", _p(x), _p(y), B, C, H, W, _s(x))
+    return y
+
+
 class _SwitchWatch(type(sys)):
     """this module's type: assigning any of its attributes (ops.WINO4 = False, monkeypatch.setattr(ops, ...), dp's
     ops.SYNC_BN = sync) forgets the memoised routes"""

@@ -1,0 +1,375 @@
+"""GPU checks of the style variant's layers: the kernels of csrc/style.hip through sivae_hip.ops.style_*, the autograd
+Functions of sivae_hip.style and the drop-in blocks of style_soft_intro_vae/blocks.py, against the float64 oracle
+tests/style_oracle.py and the fixture recorded from the reference (tests/golden/style_blocks.npz).
+
+Tolerances.  Forward outputs: the project's element-wise criterion |a - ref| <= 1e-4 |ref| + 1e-5 max |ref| (O.viol).
+Gradients: the normalised error O.nerr (against the larger of the result and, for the decoder's dx / dbias / dnw, the
+size of the terms their difference is made of) is held to GRAD_GATE, which comes from what a float32 torch restatement of
+the same formulas loses on the CPU against the float64 one over the same cases, NOT from the kernels' own error:
+
+    cd tests && python style_oracle.py
+    float32 restatement vs float64 over CASES: forward 2.284e-07, gradients 6.452e-05
+
+(the worst is dbias at [1, 1, 256, 256], a sum of 65536 terms that nearly cancel).  The gate is 4 x that figure for the
+different summation order of a parallel reduction, and never looser than the forward criterion's 1e-4."""
+import functools
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import style_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+FP32_GRAD_LOSS = 6.452e-05                      # measured, see above
+GRAD_GATE = min(4 * FP32_GRAD_LOSS, 1e-4)       # = 1e-4
+BLOCK_GRAD_GATE = 1e-4                          # a block chains convolutions and layers: the project's fp32 figure (test_e2e_gpu.TOL)
+HERE = os.path.dirname(os.path.abspath(__file__))
+BLOCKS_DIR = os.path.join(os.path.dirname(HERE), "soft-intro-vae-pytorch_amd", "style_soft_intro_vae")
+DEV = "cuda:0"
+
+
+def put(t):
+    return None if t is None else t.float().to(DEV).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def dec_case(case, mode, layer, zero_nw):
+    """(inputs, float64 reference), computed once and shared"""
+    d = O.dec_inputs(case, mode, zero_nw)
+    return d, O.dec_reference(d, mode, layer)
+
+
+@functools.lru_cache(maxsize=None)
+def enc_case(case):
+    d = O.enc_inputs(case)
+    return d, O.enc_reference(d)
+
+
+def run_dec(d, mode, layer, wants=(True, True, True, True)):
+    from sivae_hip import ops
+    x, nz, nw, b, st, g = (put(d[k]) for k in ("x", "noise", "noise_weight", "bias", "style", "g"))
+    y, m, r = ops.style_dec_fwd(x, nz, nw, b, st, mode, layer)
+    dx, dnw, db, ds = ops.style_dec_bwd(g, x, nz, nw, b, st, m, r, mode, layer, *wants)
+    return dict(y=y, m=m, r=r, dx=dx, dnw=dnw, dbias=db, dstyle=ds)
+
+
+def run_enc(d, wants=(True, True)):
+    from sivae_hip import ops
+    x, b, g, gm, gs = (put(d[k]) for k in ("x", "bias", "g", "gm", "gs"))
+    xn, m, std = ops.style_enc_fwd(x, b)
+    dx, db = ops.style_enc_bwd(g, gm, gs, x, b, m, std, 1e-5, *wants)
+    return dict(xn=xn, m=m, std=std, dx=dx, dbias=db)
+
+
+# ------------------------------------------------------------------------------------------------ the ops against the oracle
+@pytest.mark.parametrize("variant", O.DEC_VARIANTS, ids=lambda v: "mode%d-layer%d%s" % (v[0], v[1], "-nw0" if v[2] else ""))
+@pytest.mark.parametrize("case", O.CASES, ids=lambda c: "x".join(map(str, c)))
+def test_style_layer_against_the_oracle(case, variant):
+    mode, layer, zero_nw = variant
+    d, ref = dec_case(case, mode, layer, zero_nw)
+    got = run_dec(d, mode, layer)
+    v = O.viol(got["y"], ref["y"])
+    errs = {k: O.nerr(got[k], ref[k], ref["lead"] if k in O.LEAD_KEYS else 0.0)
+            for k in ("dx", "dnw", "dbias", "dstyle") if ref[k] is not None}
+    print("style_layer %s mode %d layer %d: y %.3f of the criterion; %s (gate %.1e)"
+          % (case, mode, layer, v, ", ".join("%s %.2e" % kv for kv in errs.items()), GRAD_GATE))
+    assert v <= 1.0
+    assert (got["dnw"] is None) == (mode == 0)
+    for k, e in errs.items():
+        assert e <= GRAD_GATE, (k, e)
+    if zero_nw:  # (the gradient with respect to a zero noise weight is not zero)
+        assert float(got["dnw"].abs().max()) > 0 and float(ref["dnw"].abs().max()) > 0
+
+
+@pytest.mark.parametrize("case", O.CASES, ids=lambda c: "x".join(map(str, c)))
+def test_stat_norm_against_the_oracle(case):
+    d, ref = enc_case(case)
+    got = run_enc(d)
+    vs = {k: O.viol(got[k], ref[k]) for k in ("xn", "m", "std")}
+    errs = {k: O.nerr(got[k], ref[k]) for k in ("dx", "dbias")}
+    print("stat_norm %s: %s of the criterion; %s (gate %.1e)" % (case, ", ".join("%s %.3f" % kv for kv in vs.items()),
+                                                                 ", ".join("%s %.2e" % kv for kv in errs.items()), GRAD_GATE))
+    assert max(vs.values()) <= 1.0
+    assert max(errs.values()) <= GRAD_GATE
+
+
+def test_batch_constant_noise_is_broadcast():
+    """mode 2 equals mode 1 on the noise plane repeated over the batch, bit for bit, and the plane does matter"""
+    d, _ = dec_case((3, 5, 5, 7), 2, 0, False)
+    got = run_dec(d, 2, 0)
+    rep = dict(d, noise=d["noise"].expand(3, 1, 5, 7).contiguous())
+    same = run_dec(rep, 1, 0)
+    for k in ("y", "m", "r", "dx", "dnw", "dbias", "dstyle"):
+        assert torch.equal(got[k], same[k]), k
+    other = run_dec(dict(d, noise=torch.zeros_like(d["noise"])), 2, 0)
+    assert not torch.equal(got["y"], other["y"])
+    for b in (1, 2):  # (every sample saw the one plane: its own copy of the plane gives its own result)
+        one = run_dec({k: (v if k in ("noise", "noise_weight", "bias") else v[b:b + 1]) for k, v in d.items()}, 2, 0)
+        assert torch.equal(one["y"], got["y"][b:b + 1])
+
+
+@pytest.mark.parametrize("mode", [1, 0])
+def test_every_combination_of_wanted_gradients(mode):
+    d, _ = dec_case((3, 5, 5, 7), mode, 0, False)
+    full = run_dec(d, mode, 0)
+    keys = ("dx", "dnw", "dbias", "dstyle")
+    for bits in range(16):
+        wants = tuple(bool(bits >> i & 1) for i in range(4))
+        got = run_dec(d, mode, 0, wants)
+        for k, w in zip(keys, wants):
+            if w and not (k == "dnw" and mode == 0):
+                assert torch.equal(got[k], full[k]), (wants, k)
+            else:
+                assert got[k] is None, (wants, k)
+    e, _ = enc_case((3, 5, 5, 7))
+    full = run_enc(e)
+    for wants in ((True, False), (False, True), (False, False)):
+        got = run_enc(e, wants)
+        for k, w in zip(("dx", "dbias"), wants):
+            assert (torch.equal(got[k], full[k]) if w else got[k] is None), (wants, k)
+
+
+def test_missing_upstream_gradients_are_zeros():
+    from sivae_hip import ops
+    e, _ = enc_case((2, 3, 8, 8))
+    x, b, g, gm, gs = (put(e[k]) for k in ("x", "bias", "g", "gm", "gs"))
+    xn, m, std = ops.style_enc_fwd(x, b)
+    z4, z2 = torch.zeros_like(g), torch.zeros_like(gm)
+    for a in ((None, gm, gs), (g, None, gs), (g, gm, None), (None, None, gs), (None, None, None)):
+        got = ops.style_enc_bwd(*a, x, b, m, std)
+        want = ops.style_enc_bwd(z4 if a[0] is None else a[0], z2 if a[1] is None else a[1], z2 if a[2] is None else a[2],
+                                 x, b, m, std)
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+
+def test_constant_plane_is_exact():
+    """a plane of the constant 0.5 at 8 x 8: every sum is exact, so the normalised value is exactly 0, y is the style's
+    shift bit for bit, and the encoder's std is exactly 0 with finite gradients (the dstd term is dropped there)"""
+    from sivae_hip import ops
+    B, C = 2, 3
+    g = torch.Generator().manual_seed(5)
+    x = torch.full((B, C, 8, 8), 0.5, device=DEV)
+    zero = torch.zeros(C, device=DEV)
+    st, nz, dy = (torch.randn(*s, generator=g).to(DEV) for s in ((B, 2 * C), (B, 1, 8, 8), (B, C, 8, 8)))
+    y, m, r = ops.style_dec_fwd(x, nz, zero, zero, st, 1)
+    assert torch.equal(y, st[:, C:, None, None].expand(B, C, 8, 8)) and torch.equal(m, torch.full_like(m, 0.5))
+    assert all(bool(torch.isfinite(t).all()) for t in ops.style_dec_bwd(dy, x, nz, zero, zero, st, m, r, 1))
+    xn, m, std = ops.style_enc_fwd(x, zero)
+    assert torch.equal(xn, torch.zeros_like(xn)) and torch.equal(m, torch.full_like(m, 0.5))
+    assert torch.equal(std, torch.zeros_like(std))
+    gm, gs = (torch.randn(B, C, generator=g).to(DEV) for _ in range(2))
+    dx, db = ops.style_enc_bwd(dy, gm, gs, x, zero, m, std)
+    assert bool(torch.isfinite(dx).all()) and bool(torch.isfinite(db).all())
+    # what is left: dt = (dxn - mean dxn) / sqrt(eps) + dmean / HW, the slope 1 (t = 0.5 > 0)
+    want = (dy.double() - dy.double().mean((2, 3), keepdim=True)) / np.sqrt(1e-5) + gm.double()[:, :, None, None] / 64
+    assert O.nerr(dx, want) <= GRAD_GATE
+    assert torch.equal(dx, ops.style_enc_bwd(dy, gm, None, x, zero, m, std)[0])
+
+
+def test_two_runs_are_bit_identical():
+    for case in ((3, 5, 5, 7), (1, 1, 256, 256)):
+        d, _ = dec_case(case, 1, 0, False)
+        a, b = run_dec(d, 1, 0), run_dec(d, 1, 0)
+        assert all(torch.equal(a[k], b[k]) for k in a)
+        e, _ = enc_case(case)
+        a, b = run_enc(e), run_enc(e)
+        assert all(torch.equal(a[k], b[k]) for k in a)
+
+
+@pytest.mark.parametrize("case", [(3, 5, 5, 7), (3, 2, 64, 64), (3, 2, 8, 8)], ids=lambda c: "x".join(map(str, c)))
+def test_a_sample_does_not_depend_on_the_batch(case):
+    """sample 1 of a B = 3 call against the same sample run alone"""
+    d = O.dec_inputs(case, 1)
+    whole = run_dec(d, 1, 0)
+    alone = run_dec({k: (v if k in ("noise_weight", "bias") else v[1:2]) for k, v in d.items()}, 1, 0)
+    for k in ("y", "m", "r", "dx", "dstyle"):
+        assert torch.equal(whole[k][1:2], alone[k]), k
+    e = O.enc_inputs(case)
+    whole = run_enc(e)
+    alone = run_enc({k: (v if k == "bias" else v[1:2]) for k, v in e.items()})
+    for k in ("xn", "m", "std", "dx"):
+        assert torch.equal(whole[k][1:2], alone[k]), k
+
+
+def test_alignment_changes_no_bit():
+    """the same tensors at a base that is only 4-byte aligned (the scalar instantiation) against the 16-byte path"""
+    from sivae_hip import ops
+
+    def shifted(t):  # one element behind a 512-byte aligned base
+        buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+        v = buf[1:].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        return v
+
+    for case in ((2, 3, 8, 8), (2, 2, 64, 64), (1, 2, 128, 128)):
+        d = O.dec_inputs(case, 1)
+        x, nz, nw, b, st, g = (put(d[k]) for k in ("x", "noise", "noise_weight", "bias", "style", "g"))
+        y, m, r = ops.style_dec_fwd(x, nz, nw, b, st, 1)
+        y2, m2, r2 = ops.style_dec_fwd(shifted(x), shifted(nz), nw, b, st, 1)
+        assert torch.equal(y, y2) and torch.equal(m, m2) and torch.equal(r, r2)
+        for a, a2 in zip(ops.style_dec_bwd(g, x, nz, nw, b, st, m, r, 1),
+                         ops.style_dec_bwd(shifted(g), shifted(x), nz, nw, b, st, m, r, 1)):
+            assert torch.equal(a, a2)
+        xn, m, std = ops.style_enc_fwd(x, b)
+        for a, a2 in zip((xn, m, std), ops.style_enc_fwd(shifted(x), b)):
+            assert torch.equal(a, a2)
+        for a, a2 in zip(ops.style_enc_bwd(g, m, std, x, b, m, std), ops.style_enc_bwd(shifted(g), m, std, shifted(x), b, m, std)):
+            assert torch.equal(a, a2)
+
+
+# ------------------------------------------------------------------------------------------------ the blur
+@pytest.mark.parametrize("case", O.CASES + [(2, 3, 1, 5), (1, 2, 7, 1)], ids=lambda c: "x".join(map(str, c)))
+def test_blur_against_conv2d_and_is_its_own_adjoint(case):
+    from sivae_hip import ops
+    g = torch.Generator().manual_seed(sum(case))
+    x, z = (torch.randn(*case, generator=g, dtype=torch.float64).float() for _ in range(2))
+    bx, bz = ops.style_blur(x.to(DEV)), ops.style_blur(z.to(DEV))
+    assert O.viol(bx, O.blur(x.double())) <= 1.0 and O.viol(bz, O.blur(z.double())) <= 1.0
+    # <blur x, z> = <x, blur z>: every output is eight fp32 additions and a scaling of exact products, within 2^-21 of the
+    # sum of its terms' magnitudes, which is at most blur |x|: the two inner products differ by that much of their terms
+    lhs, rhs = (bx.double().cpu() * z.double()).sum(), (x.double() * bz.double().cpu()).sum()
+    scale = (O.blur(x.double().abs()) * z.double().abs()).sum() + (x.double().abs() * O.blur(z.double().abs())).sum()
+    assert abs(float(lhs - rhs)) <= 2.0 ** -21 * float(scale)
+
+
+# ------------------------------------------------------------------------------------------------ autograd
+def test_autograd_round_trip():
+    """blur -> style_layer -> stat_norm through torch.autograd against the oracle's autograd in float64"""
+    from sivae_hip import style
+    case = (2, 3, 6, 10)
+    d, e = O.dec_inputs(case, 1), O.enc_inputs(case)
+
+    def chain(blur, layer, norm, x, nw, b1, st, nz, b2):
+        xn, m, std = norm(layer(blur(x), nw, b1, st, nz, 1, 2), b2)
+        return xn, m, std
+
+    def leaves(cast):
+        return [cast(t).requires_grad_(True) for t in (d["x"], d["noise_weight"].view(1, 3, 1, 1), d["bias"].view(1, 3, 1, 1),
+                                                       d["style"], e["bias"].view(1, 3, 1, 1))]
+
+    ref_in = leaves(lambda t: t.clone())
+    outs = chain(O.blur, lambda x, nw, b, st, nz, mode, layer: O.style_layer(x, nw.flatten(), b.flatten(), st, nz, mode, layer),
+                 lambda x, b: O.stat_norm(x, b.flatten()), *ref_in[:4], d["noise"], ref_in[4])
+    sum((o * w).sum() for o, w in zip(outs, (e["g"], e["gm"], e["gs"]))).backward()
+    got_in = leaves(put)
+    got = chain(style.blur, lambda x, nw, b, st, nz, mode, layer: style.style_layer(x, nw, b, st, nz, True, layer),
+                style.stat_norm, *got_in[:4], put(d["noise"]), got_in[4])
+    sum((o * put(w)).sum() for o, w in zip(got, (e["g"], e["gm"], e["gs"]))).backward()
+    for o, r in zip(got, outs):
+        assert O.viol(o, r) <= 1.0
+    for a, r in zip(got_in, ref_in):
+        assert a.grad.shape == a.shape and O.nerr(a.grad, r.grad) <= BLOCK_GRAD_GATE
+    # under no_grad and with nothing requiring a gradient the Functions still run
+    with torch.no_grad():
+        assert torch.equal(style.blur(got_in[0]), style.blur(got_in[0].detach()))
+
+
+# ------------------------------------------------------------------------------------------------ the blocks
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(HERE, "golden", "style_blocks.npz"))
+
+
+@pytest.fixture(scope="module")
+def blocks():
+    sys.path.insert(0, BLOCKS_DIR)
+    try:
+        import blocks as B
+    finally:
+        sys.path.remove(BLOCKS_DIR)
+    return B
+
+
+@pytest.mark.parametrize("case", ["dec_per_sample", "dec_batch_constant", "dec_no_noise", "dec_no_first_conv", "enc", "enc_last"])
+def test_blocks_against_the_reference(fx, blocks, monkeypatch, case):
+    """the drop-in blocks on the GPU against the fixture recorded from the reference's net.py, the recorded noise fed
+    through a patched torch.randn (which also checks the shapes and the order of the draws)"""
+    meta = json.loads(str(fx[case + "/meta"]))
+    pre = case + "/param/"
+    m = getattr(blocks, meta["block"])(**meta["kwargs"])
+    m.load_state_dict({k[len(pre):]: torch.from_numpy(fx[k]).float() for k in fx.files if k.startswith(pre)}, strict=True)
+    m = m.to(DEV)
+    pin = case + "/in/"
+    ins = {k[len(pin):]: put(torch.from_numpy(fx[k])).requires_grad_(True) for k in fx.files if k.startswith(pin)}
+    queue = [fx["%s/noise%d" % (case, i)] for i in range(2)] if meta["noise"] else []
+    drawn = []
+
+    def randn(shape, device=None, **kw):
+        nz = queue[len(drawn)]
+        assert list(shape) == list(nz.shape) and str(device).startswith("cuda")
+        drawn.append(1)
+        return torch.from_numpy(nz).float().to(device)
+
+    monkeypatch.setattr(torch, "randn", randn)
+    outs = m(ins["x"], ins["s1"], ins["s2"], meta["noise"]) if meta["block"] == "DecodeBlock" else m(ins["x"])
+    monkeypatch.undo()
+    assert len(drawn) == len(queue)
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    sum((o * put(torch.from_numpy(fx["%s/g%d" % (case, i)]))).sum() for i, o in enumerate(outs)).backward()
+    worst_v = max(O.viol(o, torch.from_numpy(fx["%s/out%d" % (case, i)])) for i, o in enumerate(outs))
+    pg = case + "/grad/"
+    have = dict(list(ins.items()) + list(m.named_parameters()))
+    errs = {k[len(pg):]: O.nerr(have[k[len(pg):]].grad, torch.from_numpy(fx[k])) for k in fx.files if k.startswith(pg)}
+    print("%s: outputs %.3f of the criterion, gradients worst %.2e (%s; gate %.1e)"
+          % (case, worst_v, max(errs.values()), max(errs, key=errs.get), BLOCK_GRAD_GATE))
+    assert worst_v <= 1.0
+    assert max(errs.values()) <= BLOCK_GRAD_GATE, errs
+    for k, p in m.named_parameters():  # (a parameter the reference gave no gradient gets none here)
+        assert (p.grad is not None) == ((pg + k) in fx.files), k
+
+
+def test_blocks_follow_an_optimizer_step(blocks):
+    """the packed weights are rebuilt after a stock optimizer's in-place step"""
+    torch.manual_seed(0)
+    m = blocks.EncodeBlock(6, 8, 16, False, False).to(DEV)
+    opt = torch.optim.SGD(m.parameters(), lr=0.5)
+    x = torch.randn(2, 6, 8, 8, device=DEV)
+    before = m(x)[0].detach().clone()
+    m(x)[0].square().mean().backward()
+    opt.step()
+    after = m(x)[0].detach()
+    P = {k: v.detach().double().cpu() for k, v in m.state_dict().items()}
+    assert not torch.equal(before, after)
+    assert O.viol(after, O.encode_block(P, x.double().cpu())[0]) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------ guarded
+def test_guarded():
+    """every op on guarded, poisoned outputs and exact workspaces, the inputs placed one element behind an aligned base:
+    nothing written outside a tensor, no element left at the poison value, the unguarded results"""
+    from sivae_hip import ops
+    from support.guard import describe, guarded
+    for case in ((3, 5, 5, 7), (2, 3, 8, 8), (1, 2, 128, 128), (4, 130, 4, 4)):
+        d, e = O.dec_inputs(case, 1), O.enc_inputs(case)
+        base_d, base_e = run_dec(d, 1, 0), run_enc(e)
+        base_0 = run_dec(dict(d, noise=None), 0, 1)
+        base_b = ops.style_blur(put(d["x"]))
+        for off in (0, 1):
+            with guarded(ops) as g:
+                pl = lambda t: None if t is None else g.place(put(t), offset_elems=off)  # noqa: E731
+                x, nz, nw, b, st, gy = (pl(d[k]) for k in ("x", "noise", "noise_weight", "bias", "style", "g"))
+                y, m, r = ops.style_dec_fwd(x, nz, nw, b, st, 1)
+                got_d = (y, m, r) + ops.style_dec_bwd(gy, x, nz, nw, b, st, m, r, 1)
+                y0, m0, r0 = ops.style_dec_fwd(x, None, None, b, st, 0, 1)
+                got_0 = (y0, m0, r0) + ops.style_dec_bwd(gy, x, None, None, b, st, m0, r0, 0, 1)
+                ex, eb, eg, egm, egs = (pl(e[k]) for k in ("x", "bias", "g", "gm", "gs"))
+                xn, em, es = ops.style_enc_fwd(ex, eb)
+                got_e = (xn, em, es) + ops.style_enc_bwd(eg, egm, egs, ex, eb, em, es)
+                got_b = ops.style_blur(x)
+                damage = g.verify()
+                assert not damage, "guard damage:\n%s" % describe(damage)
+            for got, base, keys in ((got_d, base_d, ("y", "m", "r", "dx", "dnw", "dbias", "dstyle")),
+                                    (got_0, base_0, ("y", "m", "r", "dx", "dnw", "dbias", "dstyle")),
+                                    (got_e, base_e, ("xn", "m", "std", "dx", "dbias"))):
+                for t, k in zip(got, keys):
+                    if base[k] is None:
+                        assert t is None
+                    else:
+                        assert bool(torch.isfinite(t).all()) and torch.equal(t, base[k]), (case, off, k)
+            assert torch.equal(got_b, base_b)
