@@ -964,6 +964,39 @@ int sivae_style_enc_bwd(const float* dxn, const float* dmean, const float* dstd,
  * first, (l + 2 c) + r, then (top + 2 mid) + bottom, times 1 / 16. */
 int sivae_style_blur(const float* x, float* y, int B, int C, int H, int W, sivae_stream_t stream);
 
+/* ---- multi-tensor launches for the style variant's optimizer (multi_tensor.hip) ----------------------------------------
+ * One launch walks many float32 tensors.  The lists are HOST arrays of n_tensors entries: device addresses as uint64,
+ * element counts as size_t, step sizes as float.  A launch carries its share of the list BY VALUE in the kernel
+ * arguments (sivae_mt_table_bytes() <= 4096 of them): at most sivae_mt_max_tensors() tensors and sivae_mt_max_chunks()
+ * chunks of sivae_mt_chunk_elems() elements, one block per chunk; a longer list is cut into as many launches as it needs
+ * and a tensor of more chunks than a launch has room for goes on in the next one (sivae_mt_launches() says how many
+ * launches a list of element counts takes; it touches no device).  Nothing is allocated, copied or synchronised, there
+ * are no atomics and no workspace.  A tensor whose addresses are all 16-byte aligned is walked with 16-byte accesses,
+ * any other with scalar ones over the same elements: an element's result depends on its own inputs alone, so a tensor
+ * is bit-identical alone, among others, at any 4-byte-aligned address and across a cut between two launches.
+ * Refused before any launch: SIVAE_ERR_SHAPE for a negative n_tensors or an address that is not 4-byte aligned,
+ * SIVAE_ERR_NULL for a null array or a null address of a tensor with elements, SIVAE_ERR_RANGE for beta2 outside
+ * [0, 1), a non-finite one_minus_beta2, a negative or non-finite eps, a non-finite weight.  n_tensors == 0 and tensors
+ * of zero elements are legal and launch nothing.
+ *
+ * sivae_mt_lreq_adam replaces the loop of style_soft_intro_vae/custom_adam.py:52-95 (LREQAdam.step: mul_, addcmul_,
+ * sqrt, add_, addcdiv_ per tensor) for the tensors that have a gradient; per element, every operation rounded to fp32
+ * with IEEE square root and division and no contraction:
+ *   v <- beta2 v + one_minus_beta2 (g g);   p <- p - step_sizes[t] (g / (sqrtf(v) + eps))
+ * with step_sizes[t] = lr sqrt(1 - beta2^step) lr_equalization_coef formed by the caller in double.  No clamps: a
+ * non-finite g makes that element of p and v non-finite and no other. */
+int sivae_mt_max_tensors(void);
+int sivae_mt_max_chunks(void);
+int sivae_mt_chunk_elems(void);
+int sivae_mt_table_bytes(void);
+int sivae_mt_launches(const void* numel, int n_tensors);
+int sivae_mt_lreq_adam(const void* params, const void* grads, const void* exp_avg_sq, const void* numel,
+                       const void* step_sizes, int n_tensors, float beta2, float one_minus_beta2, float eps,
+                       sivae_stream_t stream);
+/* sivae_mt_lerp replaces the loop body of style_soft_intro_vae/model.py:328-329 (p.data.lerp_(p_other.data, w)), torch's
+ * formula with d = src - dst:  |w| < 0.5: dst <- dst + w d;  otherwise: dst <- src - d (1 - w), 1 - w formed in fp32. */
+int sivae_mt_lerp(const void* dst, const void* src, const void* numel, int n_tensors, float weight, sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

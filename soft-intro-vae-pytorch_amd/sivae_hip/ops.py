@@ -10,6 +10,7 @@ import functools
 import os
 import sys
 
+import numpy as np
 import torch
 
 from . import lib as _lib
@@ -1649,6 +1650,73 @@ def style_blur(x):
     y = torch.empty_like(x)
     _lib.call("sivae_style_blur", _p(x), _p(y), B, C, H, W, _s(x))
     return y
+
+
+# ------------------------------------------------------------------------------------------------ multi-tensor launches (multi_tensor.hip)
+def _mt_f32(who, lists):
+    """the tensor lists of a multi-tensor call: same length, and per index float32, contiguous, on ONE ROCm device and
+    of one element count -> (device, element counts)"""
+    if len({len(l) for l in lists}) > 1:
+        raise ValueError("sivae_hip.%s: the tensor lists differ in length: %s" % (who, [len(l) for l in lists]))
+    dev = None
+    for ts in zip(*lists):
+        for t in ts:
+            _require_device(who, "multi-tensor", t)
+            if t.dtype != torch.float32:
+                raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
+            if not t.is_contiguous():
+                raise ValueError("sivae_hip.%s: tensor must be contiguous" % who)
+            if t.numel() != ts[0].numel():
+                raise ValueError("sivae_hip.%s: element counts differ: %s against %s"
+                                 % (who, tuple(t.shape), tuple(ts[0].shape)))
+            dev = dev or t.device
+            if t.device != dev:
+                raise ValueError("sivae_hip.%s: tensors on %s and on %s" % (who, dev, t.device))
+    return dev, np.array([t.numel() for t in lists[0]], dtype=np.uintp)
+
+
+def _mt_addresses(tensors):
+    return np.array([t.data_ptr() for t in tensors], dtype=np.uint64)
+
+
+def _np(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def mt_launches(numel):
+    """launches a multi-tensor call makes for these element counts (host only)"""
+    n = np.ascontiguousarray(numel, dtype=np.uintp)
+    rc = _lib.load().sivae_mt_launches(_np(n), len(n))
+    if rc < 0:
+        raise _lib.SivaeError("sivae_mt_launches", rc)
+    return rc
+
+
+def mt_lreq_adam(params, grads, states, step_sizes, beta2, eps):
+    """One LREQAdam step of every listed tensor in place (params and states = exp_avg_sq are written, grads are read):
+    v <- beta2 v + (1 - beta2) g g;  p <- p - step_sizes[t] g / (sqrt(v) + eps).  step_sizes: one Python float per tensor
+    (lr sqrt(1 - beta2^step) coef, formed in double).  On the current stream of the tensors' device; nothing is
+    allocated on the device, copied or synchronised.  -> the number of launches"""
+    if len(step_sizes) != len(params):
+        raise ValueError("sivae_hip.mt_lreq_adam: %d step sizes for %d tensors" % (len(step_sizes), len(params)))
+    dev, n = _mt_f32("mt_lreq_adam", (params, grads, states))
+    if dev is None:
+        return 0
+    p, g, v = _mt_addresses(params), _mt_addresses(grads), _mt_addresses(states)
+    s = np.array(step_sizes, dtype=np.float64).astype(np.float32)
+    _lib.call("sivae_mt_lreq_adam", _np(p), _np(g), _np(v), _np(n), _np(s), len(n), float(beta2), float(1.0 - beta2),
+              float(eps), _s(params[0]))
+    return mt_launches(n)
+
+
+def mt_lerp_(dst, src, weight):
+    """dst[t].lerp_(src[t], weight) for every listed pair in place, torch's formula.  -> the number of launches"""
+    dev, n = _mt_f32("mt_lerp_", (dst, src))
+    if dev is None:
+        return 0
+    d, q = _mt_addresses(dst), _mt_addresses(src)
+    _lib.call("sivae_mt_lerp", _np(d), _np(q), _np(n), len(n), float(weight), _s(dst[0]))
+    return mt_launches(n)
 
 
 class _SwitchWatch(type(sys)):
