@@ -964,6 +964,58 @@ int sivae_style_enc_bwd(const float* dxn, const float* dmean, const float* dstd,
  * first, (l + 2 c) + r, then (top + 2 mid) + bottom, times 1 / 16. */
 int sivae_style_blur(const float* x, float* y, int B, int C, int H, int W, sivae_stream_t stream);
 
+/* ---- the style variant's RGB layers and the level-of-detail blend (rgb.hip) -------------------------------------------
+ * ToRGB and FromRGB of style_soft_intro_vae/net.py with what Generator.decode2 and the encoders' encode2 do around them
+ * while a new resolution fades in.  float32, NCHW contiguous.  K is the image channel count, 1 <= K <= 4
+ * (SIVAE_ERR_SHAPE otherwise), C >= 1 the feature channel count, B <= 65535 and H W <= 2^30 - 1 (SIVAE_ERR_RANGE).
+ *   lrelu2(t) = lrelu_0.2(lrelu_0.2(t)); its derivative is 1 for t > 0 and 0.04 otherwise (torch's rule twice).
+ *   lerp(a, b, s) is torch's scalar-weight formula: |s| < 0.5: a + s (b - a); otherwise b - (b - a)(1 - s), 1 - s in fp32.
+ *   up2 is nearest-neighbour 2x upsampling; avg2 the 2 x 2 average ((p00 + p01) + (p10 + p11)) / 4.
+ * Every pointer must be 4-byte aligned (SIVAE_ERR_SHAPE); where every tensor that is walked plane-wise is 16-byte aligned
+ * and the plane size a multiple of 4 the kernels use 16-byte accesses, anywhere else guarded scalar ones over the same
+ * partition, so the alignment changes no bit.  No atomics; every sum runs in an order fixed by (C, H W): two runs are
+ * bit-identical and a sample's forward result does not depend on the batch.  Each tensor of C planes is read at most once
+ * per direction.  Null pointers, shapes, flags and workspaces are refused before any launch.
+ *
+ * sivae_to_rgb_fwd (net.py:229-231, and :563-571 with prev): x [B][C][H][W], w [K][C], bias [K] -> y [B][K][H][W]
+ *   conv[b][k][p] = bias[k] + sum_c w[k][c] x[b][c][p]
+ *   prev == NULL: y = conv;   prev [B][K][H/2][W/2]: y = lerp(up2(prev), conv, blend)   (H, W even: SIVAE_ERR_SHAPE) */
+int sivae_to_rgb_fwd(const float* x, const float* w, const float* bias, const float* prev, float blend, float* y, int B,
+                     int C, int H, int W, int K, sivae_stream_t stream);
+/* Its backward from dy [B][K][H][W]; has_prev says whether the forward blended (0 / 1, SIVAE_ERR_MODE otherwise):
+ *   g = dy (plain);   g = dy blend (blended: d lerp / d conv = blend on both branches)
+ *   dx[b][c][p] = sum_k w[k][c] g[b][k][p];   dw[k][c] = sum_{b,p} g[b][k][p] x[b][c][p];   dbias[k] = sum_{b,p} g[b][k][p]
+ *   dprev[b][k][q] = (1 - blend) ((dy00 + dy01) + (dy10 + dy11)) over the four pixels of q   (has_prev only: SIVAE_ERR_MODE)
+ * dx, dw, dbias and dprev may each be NULL: only what is asked for is computed; x is read only for dw and may be NULL
+ * otherwise.  dw and dbias go through per-block fp32 partials in the workspace (16-byte aligned,
+ * sivae_to_rgb_bwd_workspace_bytes) that a second small launch adds in block order in fp64; SIVAE_ERR_WORKSPACE for a
+ * NULL, misaligned or too small one when either is asked for. */
+size_t sivae_to_rgb_bwd_workspace_bytes(int B, int C, int H, int W, int K);
+int sivae_to_rgb_bwd(const float* dy, const float* x, const float* w, int has_prev, float blend, float* dx, float* dw,
+                     float* dbias, float* dprev, int B, int C, int H, int W, int K, void* workspace, size_t workspace_bytes,
+                     sivae_stream_t stream);
+/* sivae_from_rgb_fwd (net.py:215-219 followed by :270-271, and :289-294 with pool and other): img [B][K][H][W],
+ * w [C][K], bias [C].  H, W are the IMAGE's; the features are Ho x Wo = H x W, or H/2 x W/2 with pool = 1 (H, W even:
+ * SIVAE_ERR_SHAPE; a pool that is not 0 / 1: SIVAE_ERR_MODE):
+ *   u = img (pool 0);   u = avg2(img) (pool 1)
+ *   t[b][c][p] = bias[c] + sum_k w[c][k] u[b][k][p];   a = lrelu2(t)
+ *   other == NULL: y = a;   other [B][C][Ho][Wo]: y = lerp(a, other, blend)
+ * Output y [B][C][Ho][Wo]. */
+int sivae_from_rgb_fwd(const float* img, const float* w, const float* bias, int pool, const float* other, float blend,
+                       float* y, int B, int C, int H, int W, int K, sivae_stream_t stream);
+/* Its backward from dy [B][C][Ho][Wo]; t is recomputed from img, nothing of C planes is saved.  has_other says whether
+ * the forward blended (0 / 1):
+ *   da = dy lrelu2'(t) (plain);   da = (dy (1 - blend)) lrelu2'(t) (blended)
+ *   dw[c][k] = sum_{b,p} da[b][c][p] u[b][k][p];   dbias[c] = sum_{b,p} da[b][c][p]
+ *   du[b][k][p] = sum_c w[c][k] da[b][c][p];   dimg = du (pool 0);   dimg = du / 4 at each of the four source pixels (pool 1)
+ *   dother = dy blend   (has_other only: SIVAE_ERR_MODE)
+ * dimg [B][K][H][W], dw, dbias and dother may each be NULL (nothing is launched when all four are).  Workspace as above,
+ * needed when dw or dbias is asked for. */
+size_t sivae_from_rgb_bwd_workspace_bytes(int B, int C, int H, int W, int K, int pool);
+int sivae_from_rgb_bwd(const float* dy, const float* img, const float* w, const float* bias, int pool, int has_other,
+                       float blend, float* dimg, float* dw, float* dbias, float* dother, int B, int C, int H, int W, int K,
+                       void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+
 /* ---- multi-tensor launches for the style variant's optimizer (multi_tensor.hip) ----------------------------------------
  * One launch walks many float32 tensors.  The lists are HOST arrays of n_tensors entries: device addresses as uint64,
  * element counts as size_t, step sizes as float.  A launch carries its share of the list BY VALUE in the kernel

@@ -1652,6 +1652,131 @@ def style_blur(x):
     return y
 
 
+STYLE_RGB_MAX_K = 4  # image channels the RGB-layer kernels of rgb.hip are built for
+
+
+def _style_rgb_f32(who, *tensors):
+    """dtypes first, so that a wrong one is named as such wherever the tensor is"""
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
+
+
+def _style_rgb_dims(who, feat, img, weight, bias, to_rgb, pool=False):
+    """feat [B, C, Ho, Wo] (or its shape), img [B, K, H, W] (or its shape), weight with K C elements ([K, C] for to_rgb,
+    [C, K] for from_rgb; the reference's [., ., 1, 1] is the same memory), bias [K] / [C] -> (B, C, H, W, K), H, W the
+    image's"""
+    fs, ims = tuple(getattr(feat, "shape", feat)), tuple(getattr(img, "shape", img))
+    if len(fs) != 4 or len(ims) != 4 or fs[0] != ims[0] or min(fs) < 1 or min(ims) < 1:
+        raise ValueError("sivae_hip.%s: expected features [B, C, H, W] and an image [B, K, H, W], got %s and %s"
+                         % (who, fs, ims))
+    B, C, K, H, W = fs[0], fs[1], ims[1], ims[2], ims[3]
+    if not 1 <= K <= STYLE_RGB_MAX_K:
+        raise ValueError("sivae_hip.%s: 1 <= K <= %d image channels, got %d" % (who, STYLE_RGB_MAX_K, K))
+    if pool and (H % 2 or W % 2):
+        raise ValueError("sivae_hip.%s: pooling needs an even H and W, got %d x %d" % (who, H, W))
+    if fs[2:] != ((H // 2, W // 2) if pool else (H, W)):
+        raise ValueError("sivae_hip.%s: features %s do not belong to the image %s (pool=%s)" % (who, fs, ims, bool(pool)))
+    lead = (K, C) if to_rgb else (C, K)
+    if weight.numel() != K * C or tuple(weight.shape[:2]) != lead or bias.numel() != lead[0]:
+        raise ValueError("sivae_hip.%s: weight %s / bias %s do not fit C = %d, K = %d"
+                         % (who, tuple(weight.shape), tuple(bias.shape), C, K))
+    return B, C, H, W, K
+
+
+def style_to_rgb_fwd(x, weight, bias, prev=None, blend=1.0):
+    """-> y [B, K, H, W] = bias + the 1x1 convolution of x [B, C, H, W] with weight [K, C]; with prev [B, K, H/2, W/2]:
+    torch.lerp(prev upsampled 2x (nearest), that, blend)"""
+    _style_rgb_f32("style_to_rgb_fwd", x, weight, bias, prev)
+    if x.dim() != 4 or weight.dim() < 2:
+        raise ValueError("sivae_hip.style_to_rgb_fwd: expected x [B, C, H, W] and weight [K, C]")
+    K = weight.shape[0]
+    B, C, H, W, K = _style_rgb_dims("style_to_rgb_fwd", x, (x.shape[0], K, x.shape[2], x.shape[3]), weight, bias, True)
+    _style_f32("style_to_rgb_fwd", x, weight, bias, prev)
+    if prev is not None and (H % 2 or W % 2 or tuple(prev.shape) != (B, K, H // 2, W // 2)):
+        raise ValueError("sivae_hip.style_to_rgb_fwd: prev must be [B, K, H/2, W/2] of an even H, W, got %s"
+                         % (tuple(prev.shape),))
+    y = torch.empty((B, K, H, W), dtype=torch.float32, device=x.device)
+    t0 = timer_begin()
+    _lib.call("sivae_to_rgb_fwd", _p(x), _p(weight), _p(bias), _p(prev), float(blend), _p(y), B, C, H, W, K, _s(x))
+    if t0 is not None:
+        timer_end(t0, "rgb_to_fwd_kernel", 2.0 * K * x.numel())
+    return y
+
+
+def style_to_rgb_bwd(dy, x, weight, has_prev=False, blend=1.0, want_dx=True, want_dw=True, want_dbias=True,
+                     want_dprev=True):
+    """-> (dx, dw [K, C], dbias [K], dprev [B, K, H/2, W/2]), None for what is not wanted (and for dprev of a forward
+    without prev)"""
+    _style_rgb_f32("style_to_rgb_bwd", dy, x, weight)
+    if x.dim() != 4 or dy.dim() != 4 or weight.dim() < 2:
+        raise ValueError("sivae_hip.style_to_rgb_bwd: expected dy [B, K, H, W], x [B, C, H, W] and weight [K, C]")
+    B, C, H, W, K = _style_rgb_dims("style_to_rgb_bwd", x, dy, weight, weight[:, 0], True)
+    _style_f32("style_to_rgb_bwd", dy, x, weight)
+    has_prev = bool(has_prev)
+    want_dprev = bool(want_dprev) and has_prev
+    if has_prev and (H % 2 or W % 2):
+        raise ValueError("sivae_hip.style_to_rgb_bwd: a blended forward has an even H and W, got %d x %d" % (H, W))
+    dx = torch.empty_like(x) if want_dx else None
+    dw = torch.empty((K, C), dtype=torch.float32, device=x.device) if want_dw else None
+    dbias = torch.empty(K, dtype=torch.float32, device=x.device) if want_dbias else None
+    dprev = torch.empty((B, K, H // 2, W // 2), dtype=torch.float32, device=x.device) if want_dprev else None
+    ws = workspace(_lib.load().sivae_to_rgb_bwd_workspace_bytes(B, C, H, W, K), x.device) if (want_dw or want_dbias) else None
+    t0 = timer_begin()
+    _lib.call("sivae_to_rgb_bwd", _p(dy), _p(x), _p(weight), int(has_prev), float(blend), _p(dx), _p(dw), _p(dbias),
+              _p(dprev), B, C, H, W, K, _p(ws), 0 if ws is None else ws.numel(), _s(x))
+    if t0 is not None:
+        timer_end(t0, "rgb_to_bwd_kernel", 4.0 * K * x.numel())
+    return dx, dw, dbias, dprev
+
+
+def style_from_rgb_fwd(img, weight, bias, pool=False, other=None, blend=1.0):
+    """-> y [B, C, Ho, Wo] = lrelu_0.2(lrelu_0.2(bias + the 1x1 convolution of img [B, K, H, W] with weight [C, K])), on the
+    2 x 2 average of img with pool (Ho, Wo = H/2, W/2); with other [B, C, Ho, Wo]: torch.lerp(that, other, blend)"""
+    _style_rgb_f32("style_from_rgb_fwd", img, weight, bias, other)
+    if img.dim() != 4 or weight.dim() < 2:
+        raise ValueError("sivae_hip.style_from_rgb_fwd: expected img [B, K, H, W] and weight [C, K]")
+    pool = bool(pool)
+    Bi, _, Hi, Wi = img.shape
+    fshape = (Bi, weight.shape[0], Hi // 2, Wi // 2) if pool else (Bi, weight.shape[0], Hi, Wi)
+    B, C, H, W, K = _style_rgb_dims("style_from_rgb_fwd", fshape, img, weight, bias, False, pool)
+    _style_f32("style_from_rgb_fwd", img, weight, bias, other)
+    if other is not None and tuple(other.shape) != fshape:
+        raise ValueError("sivae_hip.style_from_rgb_fwd: other must be %s, got %s" % (fshape, tuple(other.shape)))
+    y = torch.empty(fshape, dtype=torch.float32, device=img.device)
+    t0 = timer_begin()
+    _lib.call("sivae_from_rgb_fwd", _p(img), _p(weight), _p(bias), int(pool), _p(other), float(blend), _p(y), B, C, H, W,
+              K, _s(img))
+    if t0 is not None:
+        timer_end(t0, "rgb_from_fwd_kernel", 2.0 * K * y.numel())
+    return y
+
+
+def style_from_rgb_bwd(dy, img, weight, bias, pool=False, has_other=False, blend=1.0, want_dimg=True, want_dw=True,
+                       want_dbias=True, want_dother=True):
+    """-> (dimg like img, dw [C, K], dbias [C], dother like dy), None for what is not wanted (and for dother of a forward
+    without other); the pre-activation is recomputed from img"""
+    _style_rgb_f32("style_from_rgb_bwd", dy, img, weight, bias)
+    if img.dim() != 4 or dy.dim() != 4 or weight.dim() < 2:
+        raise ValueError("sivae_hip.style_from_rgb_bwd: expected dy [B, C, Ho, Wo], img [B, K, H, W] and weight [C, K]")
+    pool, has_other = bool(pool), bool(has_other)
+    B, C, H, W, K = _style_rgb_dims("style_from_rgb_bwd", dy, img, weight, bias, False, pool)
+    _style_f32("style_from_rgb_bwd", dy, img, weight, bias)
+    want_dother = bool(want_dother) and has_other
+    dimg = torch.empty_like(img) if want_dimg else None
+    dw = torch.empty((C, K), dtype=torch.float32, device=img.device) if want_dw else None
+    dbias = torch.empty(C, dtype=torch.float32, device=img.device) if want_dbias else None
+    dother = torch.empty_like(dy) if want_dother else None
+    ws = workspace(_lib.load().sivae_from_rgb_bwd_workspace_bytes(B, C, H, W, K, int(pool)), img.device) \
+        if (want_dw or want_dbias) else None
+    t0 = timer_begin()
+    _lib.call("sivae_from_rgb_bwd", _p(dy), _p(img), _p(weight), _p(bias), int(pool), int(has_other), float(blend),
+              _p(dimg), _p(dw), _p(dbias), _p(dother), B, C, H, W, K, _p(ws), 0 if ws is None else ws.numel(), _s(img))
+    if t0 is not None:
+        timer_end(t0, "rgb_from_bwd_kernel", 6.0 * K * dy.numel())
+    return dimg, dw, dbias, dother
+
+
 # ------------------------------------------------------------------------------------------------ multi-tensor launches (multi_tensor.hip)
 def _mt_f32(who, lists):
     """the tensor lists of a multi-tensor call: same length, and per index float32, contiguous, on ONE ROCm device and

@@ -12,8 +12,21 @@ csrc/style.hip:
       reference's gradient is NaN; the kernel drops the dstd term there.
   blur(x) -> the depthwise [1, 2, 1] x [1, 2, 1] / 16 filter (net.py:49-60), its own adjoint.
 
+and the RGB layers with the level-of-detail blend on the kernels of csrc/rgb.hip:
+
+  to_rgb(x, weight, bias, prev=None, blend=1.0) -> y [B, K, H, W]
+      ToRGB (net.py:229-231): the 1x1 convolution with weight [K, C, 1, 1] plus bias [K].  With prev [B, K, H/2, W/2], the
+      previous level's image: torch.lerp(F.interpolate(prev, size=2 H), that, blend) as Generator.decode2 does
+      (net.py:563-571).  x, weight, bias and prev are differentiable; blend is a Python float.
+  from_rgb(img, weight, bias, pool=False, other=None, blend=1.0) -> y [B, C, Ho, Wo]
+      FromRGB followed by the encoders' second LeakyReLU (net.py:215-217, :270-271): the 1x1 convolution with weight
+      [C, K, 1, 1] plus bias [C], then LeakyReLU(0.2) twice.  pool=True runs it on F.avg_pool2d(img, 2, 2); with other
+      [B, C, Ho, Wo], the first block's output: torch.lerp(that, other, blend) (encode2, net.py:289-294).  img, weight,
+      bias and other are differentiable.  1 <= K <= 4 image channels.
+
 One forward and one backward launch per call (plus a small one for the sums over the batch); the activation is
-recomputed in the backward, so a layer saves its input and two [B, C] vectors.  There is no CPU path.
+recomputed in the backward, so a layer saves its input and two [B, C] vectors (an RGB layer its inputs alone).  There is
+no CPU path.
 """
 import torch
 
@@ -90,6 +103,47 @@ class BlurFn(torch.autograd.Function):
         return ops.style_blur(dy.contiguous())
 
 
+class ToRGBFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, prev, blend):
+        x = x.contiguous()
+        prev = None if prev is None else prev.contiguous()
+        y = ops.style_to_rgb_fwd(x, weight.detach().contiguous(), bias.detach().contiguous(), prev, blend)
+        ctx.blend, ctx.has_prev = blend, prev is not None
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dw, db, dp = ops.style_to_rgb_bwd(dy.contiguous(), x, weight.detach().contiguous(), ctx.has_prev, ctx.blend,
+                                              want_dx=need[0], want_dw=need[1], want_dbias=need[2],
+                                              want_dprev=ctx.has_prev and need[3])
+        return dx, None if dw is None else dw.view_as(weight), db, dp, None
+
+
+class FromRGBFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, weight, bias, pool, other, blend):
+        img = img.contiguous()
+        other = None if other is None else other.contiguous()
+        y = ops.style_from_rgb_fwd(img, weight.detach().contiguous(), bias.detach().contiguous(), pool, other, blend)
+        ctx.pool, ctx.blend, ctx.has_other = pool, blend, other is not None
+        ctx.save_for_backward(img, weight, bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        img, weight, bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        di, dw, db, do = ops.style_from_rgb_bwd(dy.contiguous(), img, weight.detach().contiguous(),
+                                                bias.detach().contiguous(), ctx.pool, ctx.has_other, ctx.blend,
+                                                want_dimg=need[0], want_dw=need[1], want_dbias=need[2],
+                                                want_dother=ctx.has_other and need[4])
+        return di, None if dw is None else dw.view_as(weight), db, None, do, None
+
+
 def style_layer(x, noise_weight, bias, style, noise=None, mode=None, layer=0, eps=1e-8):
     mode = noise_mode(mode)
     if mode != ops.STYLE_NOISE_NONE and noise is None:
@@ -103,3 +157,11 @@ def stat_norm(x, bias, eps=1e-5):
 
 def blur(x):
     return BlurFn.apply(x)
+
+
+def to_rgb(x, weight, bias, prev=None, blend=1.0):
+    return ToRGBFn.apply(x, weight, bias, prev, float(blend))
+
+
+def from_rgb(img, weight, bias, pool=False, other=None, blend=1.0):
+    return FromRGBFn.apply(img, weight, bias, bool(pool), other, float(blend))
