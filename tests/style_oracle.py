@@ -97,6 +97,13 @@ def encode_block(P, x, last=False, fused_scale=False):
 # a two-read plane; the largest plane; H W = 2; many channels on a tiny plane
 CASES = [(1, 1, 4, 4), (3, 5, 5, 7), (2, 3, 8, 8), (2, 2, 64, 64), (1, 2, 128, 128), (1, 1, 256, 256), (2, 3, 2, 1),
          (4, 130, 4, 4)]
+# One case per launch configuration (NT, EPT) of csrc/style.hip and per edge inside it, beyond what CASES holds: the top and
+# the bottom of <256, 4>; the bottom and the middle of <256, 16> (register slots skipped, a partly filled slot); the bottom,
+# the middle and the top minus one of <1024, 16>; the bottom and the middle of <1024, 64>, which the backward streams with
+# a partial last stride; the streamed forward with 16-byte chunks and with a scalar tail.  H W % 4 != 0 gives the tail.
+# tests/test_style_edges_host.py reads the thresholds from the source and says which row is missing when one moves.
+EDGE_CASES = [(2, 3, 16, 16), (1, 2, 1, 257), (2, 3, 32, 32), (1, 2, 25, 41), (1, 2, 37, 61), (1, 1, 17, 241),
+              (1, 2, 96, 100), (1, 1, 127, 129), (1, 1, 1, 16385), (1, 1, 160, 200), (1, 1, 257, 256), (1, 1, 255, 259)]
 # (mode, layer, noise_weight is zero)
 DEC_VARIANTS = [(1, 0, False), (2, 0, False), (0, 0, False), (0, 3, False), (1, 0, True)]
 
@@ -122,8 +129,9 @@ def enc_inputs(case, seed=0):
 
 
 def dec_reference(d, mode, layer, dtype=torch.float64):
-    """-> dict(y, dx, dnw (None in mode 0), dbias, dstyle) in `dtype`, and `lead`: the size of the leading term of the
-    instance norm's backward, max |r (style + 1)| max |g| (see nerr)"""
+    """-> dict(y, dx, dnw (None in mode 0), dbias, dstyle) in `dtype`, the planes' statistics m and r = 1 / sqrt(v + eps)
+    [B, C] in float64, and `lead`: the size of the leading term of the instance norm's backward, max |r (style + 1)| max |g|
+    (see nerr)"""
     x, nw, b, st = (d[k].to(dtype).clone().requires_grad_(True) for k in ("x", "noise_weight", "bias", "style"))
     nz = None if d["noise"] is None else d["noise"].to(dtype)
     y = style_layer(x, nw, b, st, nz, mode, layer)
@@ -131,9 +139,10 @@ def dec_reference(d, mode, layer, dtype=torch.float64):
     with torch.no_grad():
         B, C = x.shape[:2]
         u = x + (nw.view(1, C, 1, 1) * nz if mode else math.sqrt(layer + 1.0) * K_BUMP * torch.exp(-x * x / (2.0 * (layer + 1.0))))
-        _, v = plane_stats(lrelu(u + b.view(1, C, 1, 1)))
+        m, v = plane_stats(lrelu(u + b.view(1, C, 1, 1)))
         lead = float(((st.view(B, 2, C, 1, 1)[:, 0] + 1).abs() / torch.sqrt(v + 1e-8)).max() * d["g"].abs().max())
-    return dict(y=y.detach(), dx=x.grad, dnw=None if mode == 0 else nw.grad, dbias=b.grad, dstyle=st.grad, lead=lead)
+    return dict(y=y.detach(), dx=x.grad, dnw=None if mode == 0 else nw.grad, dbias=b.grad, dstyle=st.grad, lead=lead,
+                m=m.double().flatten(1), r=(1.0 / torch.sqrt(v.double() + 1e-8)).flatten(1))
 
 
 def enc_reference(d, dtype=torch.float64):
@@ -167,11 +176,42 @@ def viol(a, ref, rtol=1e-4, atol_scale=1e-5):
 
 LEAD_KEYS = ("dx", "dnw", "dbias")  # (the decoder gradients that come out of dt)
 
+# ------------------------------------------------------------------------------------------------ planted planes
+PLANT_STRIDES = (256, 1024, 4096)  # the elements a block of 64, 256 and 1024 threads covers with one 4-element chunk each
+PLANT_CASES = EDGE_CASES + [(1, 1, 256, 256)]
+
+
+def planted(n):
+    """{flat index: value} of a plane of n elements: the first and the last element, and for every stride s with 2 s < n
+    the first element of a thread's second chunk (s) and of the last, possibly partial, round of chunks (where that round
+    is the last element alone, as at n = 1025, it carries this value).  Every value is exact in float32 and large against the unit-variance data around it, so a sum that drops one of these elements is
+    wrong by far more than any rounding."""
+    at = {0: -32.0, n - 1: 64.0}
+    for s in PLANT_STRIDES:
+        if 2 * s < n:
+            at[s] = 48.0
+            at[(n - 1) // s * s] = -24.0
+    return at
+
+
+def plant(d, keys=("x", "g")):
+    """a copy of the inputs d with planted() written into every plane of d[k], k in keys"""
+    d = dict(d)
+    for k in keys:
+        t = d[k].clone()
+        flat = t.view(t.shape[0], t.shape[1], -1)
+        for e, v in planted(flat.shape[2]).items():
+            flat[:, :, e] = v
+        d[k] = t
+    return d
+
+
 
 def fp32_loss():
-    """worst normalised error of the float32 restatement against the float64 one over CASES: (forward, gradients)"""
+    """worst normalised error of the float32 restatement against the float64 one over CASES and EDGE_CASES:
+    (forward, gradients)"""
     fwd = grad = 0.0
-    for case in CASES:
+    for case in CASES + EDGE_CASES:
         for mode, layer, zero_nw in DEC_VARIANTS:
             d = dec_inputs(case, mode, zero_nw)
             r64, r32 = dec_reference(d, mode, layer), dec_reference(d, mode, layer, torch.float32)
@@ -186,4 +226,4 @@ def fp32_loss():
 
 
 if __name__ == "__main__":
-    print("float32 restatement vs float64 over CASES: forward %.3e, gradients %.3e" % fp32_loss())
+    print("float32 restatement vs float64 over CASES and EDGE_CASES: forward %.3e, gradients %.3e" % fp32_loss())

@@ -2,7 +2,8 @@
 CPU, written from the formulas in include/sivae_hip.h, not from the kernels.  Everything runs in the dtype of its inputs
 (float64 for the checks; float32 to measure what the arithmetic itself loses); gradients come from autograd.
 
-    python style_rgb_oracle.py     prints the float32 restatement's loss against the float64 one over CASES
+    python style_rgb_oracle.py     prints the float32 restatement's loss against the float64 one over CASES and
+                                   EDGE_CASES
 """
 import torch
 import torch.nn.functional as F
@@ -56,6 +57,20 @@ CASES = [(1, 1, 4, 4, 1),        # a plane smaller than a wave; K = 1
          (2, 3, 64, 64, 3),      # a 64 x 64 plane
          (1, 2, 128, 128, 4),    # K = 4
          (1, 1, 256, 256, 3)]    # the largest plane: 65536-term dw and dbias sums
+# What CASES leaves out of csrc/rgb.hip's launch logic: K = 2; C = 9 (cpw = 2: a wave with one channel, waves that start
+# past C); K = 4 with an odd C > 8; planes of several 256-pixel tiles with a partial last one, plain and pooled; more than
+# 256 blocks, so that a thread of the merge kernel adds more than one partial.  tests/test_style_edges_host.py keeps it so.
+EDGE_CASES = [(2, 5, 6, 10, 2),       # K = 2, plain, blended and pooled
+              (1, 9, 8, 8, 2),        # K = 2; C = 9
+              (1, 2, 36, 44, 2),      # K = 2 on several tiles
+              (2, 11, 6, 10, 4),      # K = 4 (8 values a channel in the partials) with an odd C > 8
+              (2, 9, 6, 10, 3),       # C = 9 with K = 3: two channels per wave sum, an odd slice
+              (2, 3, 20, 20, 3),      # H W = 400: two tiles, the second partial, 16-byte chunks
+              (2, 3, 17, 19, 3),      # H W = 323: the same with scalar accesses (plain only)
+              (2, 3, 4, 5, 3),        # H W % 4 = 0 with an odd W: 16-byte chunks across row ends
+              (1, 3, 36, 44, 3),      # H W = 1584: 7 tiles, the last partial; pooled 18 x 22 = 396: two tiles, rows of 22
+              (300, 5, 4, 4, 3),      # 300 blocks: the merge kernel's second round, 4 values a channel, both layers
+              (259, 2, 4, 4, 4)]      # 259 blocks with 8 values a channel
 BLENDS = (0.25, 0.75)            # the two branches of torch's lerp
 KINK_MARGIN = 2.0 ** -18
 MAX_SEEDS = 64
@@ -134,9 +149,10 @@ TO_GRADS, FROM_GRADS = ("dx", "dw", "dbias", "dprev"), ("dimg", "dw", "dbias", "
 
 
 def fp32_loss():
-    """worst normalised error of the float32 restatement against the float64 one over CASES: (forward, gradients)"""
+    """worst normalised error of the float32 restatement against the float64 one over CASES and EDGE_CASES:
+    (forward, gradients)"""
     fwd = grad = 0.0
-    for case in CASES:
+    for case in CASES + EDGE_CASES:
         for blend in variants(case):
             for d, ref, keys in ((to_inputs(case, blend), to_reference, TO_GRADS),
                                  (from_inputs(case, blend), from_reference, FROM_GRADS)):
@@ -147,4 +163,4 @@ def fp32_loss():
 
 
 if __name__ == "__main__":
-    print("float32 restatement vs float64 over CASES: forward %.3e, gradients %.3e" % fp32_loss())
+    print("float32 restatement vs float64 over CASES and EDGE_CASES: forward %.3e, gradients %.3e" % fp32_loss())

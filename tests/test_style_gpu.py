@@ -5,10 +5,11 @@ tests/style_oracle.py and the fixture recorded from the reference (tests/golden/
 Tolerances.  Forward outputs: the project's element-wise criterion |a - ref| <= 1e-4 |ref| + 1e-5 max |ref| (O.viol).
 Gradients: the normalised error O.nerr (against the larger of the result and, for the decoder's dx / dbias / dnw, the
 size of the terms their difference is made of) is held to GRAD_GATE, which comes from what a float32 torch restatement of
-the same formulas loses on the CPU against the float64 one over the same cases, NOT from the kernels' own error:
+the same formulas loses on the CPU against the float64 one over the same cases and the edge cases of
+tests/test_style_edges_gpu.py (O.CASES and O.EDGE_CASES), NOT from the kernels' own error:
 
     cd tests && python style_oracle.py
-    float32 restatement vs float64 over CASES: forward 2.284e-07, gradients 6.452e-05
+    float32 restatement vs float64 over CASES and EDGE_CASES: forward 2.498e-07, gradients 6.452e-05
 
 (the worst is dbias at [1, 1, 256, 256], a sum of 65536 terms that nearly cancel).  The gate is 4 x that figure for the
 different summation order of a parallel reduction, and never looser than the forward criterion's 1e-4."""
@@ -340,36 +341,40 @@ def test_blocks_follow_an_optimizer_step(blocks):
 
 
 # ------------------------------------------------------------------------------------------------ guarded
-def test_guarded():
-    """every op on guarded, poisoned outputs and exact workspaces, the inputs placed one element behind an aligned base:
-    nothing written outside a tensor, no element left at the poison value, the unguarded results"""
+def guarded_case(case):
+    """every op at one shape on guarded, poisoned outputs and exact workspaces, the inputs placed at an aligned base and
+    one element behind it: nothing written outside a tensor, no element left at the poison value, the unguarded results"""
     from sivae_hip import ops
     from support.guard import describe, guarded
+    d, e = O.dec_inputs(case, 1), O.enc_inputs(case)
+    base_d, base_e = run_dec(d, 1, 0), run_enc(e)
+    base_0 = run_dec(dict(d, noise=None), 0, 1)
+    base_b = ops.style_blur(put(d["x"]))
+    for off in (0, 1):
+        with guarded(ops) as g:
+            pl = lambda t: None if t is None else g.place(put(t), offset_elems=off)  # noqa: E731
+            x, nz, nw, b, st, gy = (pl(d[k]) for k in ("x", "noise", "noise_weight", "bias", "style", "g"))
+            y, m, r = ops.style_dec_fwd(x, nz, nw, b, st, 1)
+            got_d = (y, m, r) + ops.style_dec_bwd(gy, x, nz, nw, b, st, m, r, 1)
+            y0, m0, r0 = ops.style_dec_fwd(x, None, None, b, st, 0, 1)
+            got_0 = (y0, m0, r0) + ops.style_dec_bwd(gy, x, None, None, b, st, m0, r0, 0, 1)
+            ex, eb, eg, egm, egs = (pl(e[k]) for k in ("x", "bias", "g", "gm", "gs"))
+            xn, em, es = ops.style_enc_fwd(ex, eb)
+            got_e = (xn, em, es) + ops.style_enc_bwd(eg, egm, egs, ex, eb, em, es)
+            got_b = ops.style_blur(x)
+            damage = g.verify()
+            assert not damage, "guard damage:\n%s" % describe(damage)
+        for got, base, keys in ((got_d, base_d, ("y", "m", "r", "dx", "dnw", "dbias", "dstyle")),
+                                (got_0, base_0, ("y", "m", "r", "dx", "dnw", "dbias", "dstyle")),
+                                (got_e, base_e, ("xn", "m", "std", "dx", "dbias"))):
+            for t, k in zip(got, keys):
+                if base[k] is None:
+                    assert t is None
+                else:
+                    assert bool(torch.isfinite(t).all()) and torch.equal(t, base[k]), (case, off, k)
+        assert torch.equal(got_b, base_b)
+
+
+def test_guarded():
     for case in ((3, 5, 5, 7), (2, 3, 8, 8), (1, 2, 128, 128), (4, 130, 4, 4)):
-        d, e = O.dec_inputs(case, 1), O.enc_inputs(case)
-        base_d, base_e = run_dec(d, 1, 0), run_enc(e)
-        base_0 = run_dec(dict(d, noise=None), 0, 1)
-        base_b = ops.style_blur(put(d["x"]))
-        for off in (0, 1):
-            with guarded(ops) as g:
-                pl = lambda t: None if t is None else g.place(put(t), offset_elems=off)  # noqa: E731
-                x, nz, nw, b, st, gy = (pl(d[k]) for k in ("x", "noise", "noise_weight", "bias", "style", "g"))
-                y, m, r = ops.style_dec_fwd(x, nz, nw, b, st, 1)
-                got_d = (y, m, r) + ops.style_dec_bwd(gy, x, nz, nw, b, st, m, r, 1)
-                y0, m0, r0 = ops.style_dec_fwd(x, None, None, b, st, 0, 1)
-                got_0 = (y0, m0, r0) + ops.style_dec_bwd(gy, x, None, None, b, st, m0, r0, 0, 1)
-                ex, eb, eg, egm, egs = (pl(e[k]) for k in ("x", "bias", "g", "gm", "gs"))
-                xn, em, es = ops.style_enc_fwd(ex, eb)
-                got_e = (xn, em, es) + ops.style_enc_bwd(eg, egm, egs, ex, eb, em, es)
-                got_b = ops.style_blur(x)
-                damage = g.verify()
-                assert not damage, "guard damage:\n%s" % describe(damage)
-            for got, base, keys in ((got_d, base_d, ("y", "m", "r", "dx", "dnw", "dbias", "dstyle")),
-                                    (got_0, base_0, ("y", "m", "r", "dx", "dnw", "dbias", "dstyle")),
-                                    (got_e, base_e, ("xn", "m", "std", "dx", "dbias"))):
-                for t, k in zip(got, keys):
-                    if base[k] is None:
-                        assert t is None
-                    else:
-                        assert bool(torch.isfinite(t).all()) and torch.equal(t, base[k]), (case, off, k)
-            assert torch.equal(got_b, base_b)
+        guarded_case(case)

@@ -5,10 +5,11 @@ reference (tests/golden/style_net.npz).
 
 Tolerances.  Forward outputs: the project's element-wise criterion |a - ref| <= 1e-4 |ref| + 1e-5 max |ref| (O.viol).
 Gradients of the ops: the normalised error O.nerr is held to GRAD_GATE, which comes from what a float32 torch restatement
-of the same formulas loses on the CPU against the float64 one over the same cases, NOT from the kernels' own error:
+of the same formulas loses on the CPU against the float64 one over the same cases and the edge cases of
+tests/test_style_edges_gpu.py (O.CASES and O.EDGE_CASES), NOT from the kernels' own error:
 
     cd tests && python style_rgb_oracle.py
-    float32 restatement vs float64 over CASES: forward 3.115e-07, gradients 1.286e-06
+    float32 restatement vs float64 over CASES and EDGE_CASES: forward 3.115e-07, gradients 1.286e-06
 
 The gate is 4 x that figure for the different summation order of a parallel reduction, and never looser than 1e-4.
 Classes chain convolutions, blocks and these layers: their gradients are held to the project's fp32 figure 1e-4
@@ -175,45 +176,54 @@ def test_two_runs_are_bit_identical():
 
 
 # ------------------------------------------------------------------------------------------------ flags
+def wanted_alone(variant, op):
+    """each gradient wanted alone, two together and none, against the run that wants them all, bit for bit"""
+    case_fn, run, keys, _ = RUN[op]
+    d, ref = case_fn(*variant)
+    full = run(d)
+    for bits in (1, 2, 4, 8, 6, 0):
+        wants = tuple(bool(bits >> i & 1) for i in range(4))
+        got = run(d, wants)
+        for k, w in zip(keys[1:], wants):
+            if w and ref[k] is not None:
+                assert torch.equal(got[k], full[k]), (variant, wants, k)
+            else:
+                assert got[k] is None, (variant, wants, k)
+
+
 @pytest.mark.parametrize("op", ["to", "from"])
 def test_each_wanted_gradient_alone(op):
-    case_fn, run, keys, _ = RUN[op]
     for variant in (((3, 5, 6, 10, 3), 0.25), ((3, 5, 5, 7, 3), None), ((1, 2, 128, 128, 4), 0.75)):
-        d, ref = case_fn(*variant)
-        full = run(d)
-        for bits in (1, 2, 4, 8, 6, 0):
-            wants = tuple(bool(bits >> i & 1) for i in range(4))
-            got = run(d, wants)
-            for k, w in zip(keys[1:], wants):
-                if w and ref[k] is not None:
-                    assert torch.equal(got[k], full[k]), (variant, wants, k)
-                else:
-                    assert got[k] is None, (variant, wants, k)
+        wanted_alone(variant, op)
 
 
 # ------------------------------------------------------------------------------------------------ guarded
-def test_guarded():
-    """every op on guarded, poisoned outputs and workspaces of exactly the reported size, the inputs placed at an aligned
-    base and one element behind it: nothing written outside a tensor, no element left at the poison value, the unguarded
-    results"""
+def guarded_variant(variant, op):
+    """one op at one shape on guarded, poisoned outputs and workspaces of exactly the reported size, the inputs placed at an
+    aligned base and one element behind it: nothing written outside a tensor, no element left at the poison value, the
+    unguarded results"""
     from sivae_hip import ops
     from support.guard import describe, guarded
+    case_fn, run, keys, _ = RUN[op]
+    d, _ = case_fn(*variant)
+    base = run(d)
+    for off in (0, 1):
+        with guarded(ops) as g:
+            got = run(d, place=lambda t: None if t is None else g.place(put(t), offset_elems=off))
+            damage = g.verify()
+            assert not damage, "guard damage (%s, %s, offset %d):\n%s" % (op, variant, off, describe(damage))
+        for k in keys:
+            if base[k] is None:
+                assert got[k] is None
+            else:
+                assert bool(torch.isfinite(got[k]).all()) and torch.equal(got[k], base[k]), (op, variant, off, k)
+
+
+def test_guarded():
     for variant in (((3, 5, 5, 7, 3), None), ((3, 5, 6, 10, 3), 0.25), ((2, 3, 2, 2, 3), 0.75), ((4, 130, 4, 4, 3), 0.25),
                     ((1, 2, 128, 128, 4), 0.75), ((1, 2, 128, 128, 4), None)):
         for op in ("to", "from"):
-            case_fn, run, keys, _ = RUN[op]
-            d, _ = case_fn(*variant)
-            base = run(d)
-            for off in (0, 1):
-                with guarded(ops) as g:
-                    got = run(d, place=lambda t: None if t is None else g.place(put(t), offset_elems=off))
-                    damage = g.verify()
-                    assert not damage, "guard damage (%s, %s, offset %d):\n%s" % (op, variant, off, describe(damage))
-                for k in keys:
-                    if base[k] is None:
-                        assert got[k] is None
-                    else:
-                        assert bool(torch.isfinite(got[k]).all()) and torch.equal(got[k], base[k]), (op, variant, off, k)
+            guarded_variant(variant, op)
 
 
 # ------------------------------------------------------------------------------------------------ autograd
