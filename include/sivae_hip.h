@@ -1049,6 +1049,51 @@ int sivae_mt_lreq_adam(const void* params, const void* grads, const void* exp_av
  * formula with d = src - dst:  |w| < 0.5: dst <- dst + w d;  otherwise: dst <- src - d (1 - w), 1 - w formed in fp32. */
 int sivae_mt_lerp(const void* dst, const void* src, const void* numel, int n_tensors, float weight, sivae_stream_t stream);
 
+/* ---- the style variant's mapping networks and style assembly (mapping.hip, and one epilogue of linear.hip) ---------------
+ * What style_soft_intro_vae/net.py and model.py leave between the latent and the networks.  fp32, rows [rows][cols]
+ * contiguous.  Every pointer must be 4-byte aligned (SIVAE_ERR_SHAPE); where every row of every tensor of a call is 16-byte
+ * aligned the kernels use 16-byte accesses, anywhere else guarded scalar ones over the same partition, so the alignment
+ * changes no bit.  No atomics, no workspace; every sum runs in an order fixed by the shape alone.  A tensor of 2^31 or
+ * more elements is SIVAE_ERR_RANGE, a non-positive size SIVAE_ERR_SHAPE, all returned before any launch.
+ *
+ * sivae_linear_lrelu_fwd: sivae_linear_fwd with LeakyReLU(slope) behind the bias (a MappingBlock, net.py:748-751):
+ *   y = v > 0 ? v : v slope, v = x W^T + bias, one multiply as torch's.  Same shapes, workspace and codes as
+ *   sivae_linear_fwd; a slope outside [0, 1] is SIVAE_ERR_MODE.  (ReLU is not this with slope 0: fmaxf differs on -0 and
+ *   NaN; sivae_linear_fwd is unchanged.) */
+int sivae_linear_lrelu_fwd(const float* x, const float* w, const float* bias, float* y, float slope, int B, int K, int N,
+                           void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+/* Its way back to the pre-activation, from the saved OUTPUT y [B][N] (its sign is the pre-activation's), with the bias
+ * gradient, in one pass over dy:
+ *   dz[b][n] = dy[b][n] (y[b][n] > 0 ? 1 : slope)   (the slope at 0 is `slope`, torch's rule)
+ *   dbias[n] = sum_b dz[b][n], ascending b, accumulated in fp64
+ * y == NULL: a layer without activation, dz = dy.  dz and dbias may each be NULL (nothing is launched when both are). */
+int sivae_lrelu_bias_bwd(const float* dy, const float* y, float slope, float* dz, float* dbias, int B, int N,
+                         sivae_stream_t stream);
+/* pixel_norm (net.py:29-30) over the rows of x [B][Z], any B, Z >= 1:
+ *   r[b] = 1 / sqrt(mean_z x[b][z]^2 + eps) (the mean and r formed in fp64, kept in rfac [B] for the backward)
+ *   y = x r;   dx = r dy - x r^3 mean_z(dy x)
+ * A row of zeros gives y = 0 and dx = dy / sqrt(eps).  eps < 0 is SIVAE_ERR_SHAPE. */
+int sivae_pixel_norm_fwd(const float* x, float* y, float* rfac, int B, int Z, float eps, sivae_stream_t stream);
+int sivae_pixel_norm_bwd(const float* dy, const float* x, const float* rfac, float* dx, int B, int Z,
+                         sivae_stream_t stream);
+/* The style assembly of SoftIntroVAEModelTL.generate (model.py:176-200) from s [B][Z] to styles [B][L][Z], in the
+ * reference's order:
+ *   update_avg = 1: avg[l] <- lerp(avg[l], mean_b s[b], avg_weight) for every l (avg [L][Z], updated in place by a first
+ *                   small launch; avg_weight = 1 - beta formed by the caller, outside [0, 1]: SIVAE_ERR_MODE; the mean runs
+ *                   in ascending b in fp64);
+ *   s2 != NULL:     layers l >= mix_cutoff take s2 [B][Z] (0 <= mix_cutoff <= L, SIVAE_ERR_SHAPE otherwise);
+ *   truncate = 1:   styles[b][l] = lerp(avg[l], styles[b][l], psi) for l < trunc_cutoff (0 <= trunc_cutoff <= L), with the
+ *                   UPDATED avg.
+ * lerp is torch's formula.  Without s2, update_avg and truncate the result is the broadcast of s, bit for bit.
+ * update_avg or truncate without avg is SIVAE_ERR_NULL; a flag that is not 0 / 1 SIVAE_ERR_MODE. */
+int sivae_styles_fwd(const float* s, const float* s2, int mix_cutoff, float* avg, int update_avg, float avg_weight,
+                     int truncate, float psi, int trunc_cutoff, float* styles, int B, int L, int Z, sivae_stream_t stream);
+/* Its backward (avg takes no gradient, as under the reference's no_grad): with c_l = psi for l < trunc_cutoff and 1 otherwise
+ *   ds[b] = sum_{l < mix_cutoff} c_l dstyles[b][l];   ds2[b] = sum_{l >= mix_cutoff} c_l dstyles[b][l]   (ascending l)
+ * has_s2 = 0: every layer belongs to ds (mix_cutoff is ignored) and a ds2 is SIVAE_ERR_MODE.  ds and ds2 may each be NULL. */
+int sivae_styles_bwd(const float* dstyles, int has_s2, int mix_cutoff, int truncate, float psi, int trunc_cutoff, float* ds,
+                     float* ds2, int B, int L, int Z, sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ struct LinArgs {
   int B, K, N;
   int S, slice_len;   // contraction slice per wave (multiple of 8)
   int relu;
+  int lrelu;          // LeakyReLU(slope) instead: v > 0 ? v : v slope (one multiply, as torch's)
+  float slope;
 };
 
 // ---- forward: out[s][b][n] (or y when S == 1)
@@ -94,6 +96,7 @@ __global__ void __launch_bounds__(64) linear_fwd_kernel(LinArgs a) {
       if (b < a.B) {
         float v = acc[r][e] + bias;
         if (a.S == 1 && a.relu) v = fmaxf(v, 0.f);
+        else if (a.S == 1 && a.lrelu) v = v > 0.f ? v : v * a.slope;
         dst[(size_t)b * a.N + n] = v;
       }
     }
@@ -215,9 +218,10 @@ __global__ void __launch_bounds__(64) linear_wgrad_kernel(LinArgs a) {
   }
 }
 
-// y[b][c] = sum_s part[s][b][c] (+ bias[c]) (ReLU)
+// y[b][c] = sum_s part[s][b][c] (+ bias[c]) (ReLU, or LeakyReLU(slope))
 __global__ void linear_reduce_kernel(const float* __restrict__ part, float* __restrict__ y,
-                                     const float* __restrict__ bias, int S, size_t numel, int cols, int relu) {
+                                     const float* __restrict__ bias, int S, size_t numel, int cols, int relu, int lrelu,
+                                     float slope) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= numel) return;
   float s0 = 0.f, s1 = 0.f;
@@ -230,6 +234,7 @@ __global__ void linear_reduce_kernel(const float* __restrict__ part, float* __re
   float v = s0 + s1;
   if (bias) v += bias[e % cols];
   if (relu) v = fmaxf(v, 0.f);
+  else if (lrelu) v = v > 0.f ? v : v * slope;
   y[e] = v;
 }
 
@@ -280,15 +285,17 @@ extern "C" size_t sivae_linear_workspace_bytes(int B, int K, int N) {
   return (f > d ? f : d) * sizeof(float) + 16;
 }
 
-extern "C" int sivae_linear_fwd(const float* x, const float* w, const float* bias, float* y, int relu, int B, int K,
-                                int N, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// the forward behind both entry points: relu (fmaxf) and lrelu (compare, multiply) are two epilogues, not one with a
+// slope of 0: they differ on -0 and NaN
+static int linear_fwd_impl(const float* x, const float* w, const float* bias, float* y, int relu, int lrelu, float slope,
+                           int B, int K, int N, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!x || !w || !y) return SIVAE_ERR_NULL;
   if (!lin_ok(B, K, N)) return SIVAE_ERR_SHAPE;
   if (B > 32 * MAX_RB) {
     for (int r0 = 0; r0 < B; r0 += 32 * MAX_RB) {
       const int nb = B - r0 < 32 * MAX_RB ? B - r0 : 32 * MAX_RB;
-      const int rc = sivae_linear_fwd(x + (size_t)r0 * K, w, bias, y + (size_t)r0 * N, relu, nb, K, N, workspace,
-                                      workspace_bytes, stream);
+      const int rc = linear_fwd_impl(x + (size_t)r0 * K, w, bias, y + (size_t)r0 * N, relu, lrelu, slope, nb, K, N,
+                                     workspace, workspace_bytes, stream);
       if (rc != SIVAE_OK) return rc;
     }
     return SIVAE_OK;
@@ -301,6 +308,8 @@ extern "C" int sivae_linear_fwd(const float* x, const float* w, const float* bia
   a.K = K;
   a.N = N;
   a.relu = relu;
+  a.lrelu = lrelu;
+  a.slope = slope;
   const int tiles = (N + 31) / 32;
   a.S = split_for(tiles, K, &a.slice_len);
   if (a.S > 1) {
@@ -316,8 +325,19 @@ extern "C" int sivae_linear_fwd(const float* x, const float* w, const float* bia
   if (rc != SIVAE_OK || a.S == 1) return rc;
   const size_t numel = (size_t)B * N;
   hipLaunchKernelGGL(linear_reduce_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, stream, a.out, y, bias,
-                     a.S, numel, N, relu);
+                     a.S, numel, N, relu, lrelu, slope);
   return sivae_launch_status();
+}
+
+extern "C" int sivae_linear_fwd(const float* x, const float* w, const float* bias, float* y, int relu, int B, int K,
+                                int N, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return linear_fwd_impl(x, w, bias, y, relu, 0, 0.f, B, K, N, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sivae_linear_lrelu_fwd(const float* x, const float* w, const float* bias, float* y, float slope, int B,
+                                      int K, int N, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (!(slope >= 0.f && slope <= 1.f)) return SIVAE_ERR_MODE;
+  return linear_fwd_impl(x, w, bias, y, 0, 1, slope, B, K, N, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sivae_linear_dgrad(const float* dy, const float* w, float* dx, int B, int K, int N, void* workspace,
@@ -341,6 +361,8 @@ extern "C" int sivae_linear_dgrad(const float* dy, const float* w, float* dx, in
   a.K = K;
   a.N = N;
   a.relu = 0;
+  a.lrelu = 0;
+  a.slope = 0.f;
   const int tiles = (K + 31) / 32;
   a.S = split_for(tiles, N, &a.slice_len);
   a.slice_len = ((a.slice_len + 7) / 8) * 8;
@@ -357,7 +379,7 @@ extern "C" int sivae_linear_dgrad(const float* dy, const float* w, float* dx, in
   if (rc != SIVAE_OK || a.S == 1) return rc;
   const size_t numel = (size_t)B * K;
   hipLaunchKernelGGL(linear_reduce_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, stream, a.out, dx,
-                     (const float*)nullptr, a.S, numel, K, 0);
+                     (const float*)nullptr, a.S, numel, K, 0, 0, 0.f);
   return sivae_launch_status();
 }
 
@@ -376,6 +398,8 @@ extern "C" int sivae_linear_wgrad(const float* dy, const float* x, float* dw, in
   a.S = 1;
   a.slice_len = 0;
   a.relu = 0;
+  a.lrelu = 0;
+  a.slope = 0.f;
   const long long nblk = (long long)((N + 31) / 32) * ((K + 127) / 128);
   hipLaunchKernelGGL(linear_wgrad_kernel, dim3((unsigned)nblk), dim3(64), 0, stream, a);
   return sivae_launch_status();

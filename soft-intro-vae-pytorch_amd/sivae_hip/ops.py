@@ -1777,6 +1777,141 @@ def style_from_rgb_bwd(dy, img, weight, bias, pool=False, has_other=False, blend
     return dimg, dw, dbias, dother
 
 
+# ------------------------------------------------------------------------------------------------ mapping networks, style assembly (mapping.hip)
+def _map_f32(who, *tensors):
+    for t in tensors:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:  # (dtypes first, so that a wrong one is named as such wherever the tensor is)
+            raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
+        _require_device(who, "mapping", t)
+        if not t.is_contiguous():
+            raise ValueError("sivae_hip.%s: tensor must be contiguous" % who)
+
+
+def _map_rows(who, x, *same):
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("sivae_hip.%s: expected rows [B, Z] with B, Z >= 1, got %s" % (who, tuple(x.shape)))
+    for t in same:
+        if t is not None and t.shape != x.shape:
+            raise ValueError("sivae_hip.%s: %s does not match %s" % (who, tuple(t.shape), tuple(x.shape)))
+    return x.shape
+
+
+def pixel_norm_fwd(x, eps=1e-8):
+    """-> (y, r [B]): y = x r with r = 1 / sqrt(mean_z x^2 + eps) per row of x [B, Z]"""
+    _map_f32("pixel_norm_fwd", x)
+    B, Z = _map_rows("pixel_norm_fwd", x)
+    y = torch.empty_like(x)
+    r = torch.empty(B, dtype=torch.float32, device=x.device)
+    _lib.call("sivae_pixel_norm_fwd", _p(x), _p(y), _p(r), B, Z, float(eps), _s(x))
+    return y, r
+
+
+def pixel_norm_bwd(dy, x, r):
+    """-> dx = r dy - x r^3 mean_z(dy x)"""
+    _map_f32("pixel_norm_bwd", dy, x, r)
+    B, Z = _map_rows("pixel_norm_bwd", x, dy)
+    if tuple(r.shape) != (B,):
+        raise ValueError("sivae_hip.pixel_norm_bwd: r must be [B] = (%d,), got %s" % (B, tuple(r.shape)))
+    dx = torch.empty_like(x)
+    _lib.call("sivae_pixel_norm_bwd", _p(dy), _p(x), _p(r), _p(dx), B, Z, _s(x))
+    return dx
+
+
+def _slope(who, slope):
+    slope = float(slope)
+    if not 0.0 <= slope <= 1.0:
+        raise ValueError("sivae_hip.%s: the LeakyReLU slope must be in [0, 1], got %r" % (who, slope))
+    return slope
+
+
+def linear_lrelu_fwd(x, w, bias=None, slope=0.2):
+    """linear_fwd with LeakyReLU(slope) as the epilogue: y = v > 0 ? v : v slope, v = x W^T + b"""
+    _require(x, w, bias)
+    slope = _slope("linear_lrelu_fwd", slope)
+    B, K = x.shape
+    N = w.shape[0]
+    ws = workspace(_lib.load().sivae_linear_workspace_bytes(B, K, N), x.device)
+    y = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    t0 = timer_begin()
+    _lib.call("sivae_linear_lrelu_fwd", _p(x), _p(w), _p(bias), _p(y), slope, B, K, N, _p(ws), ws.numel(), _s(x))
+    if t0 is not None:
+        timer_end(t0, "linear_fwd_kernel", 2.0 * B * K * N)
+    return y
+
+
+def lrelu_bias_bwd(dy, y=None, slope=0.2, want_dz=True, want_dbias=True, out=None):
+    """-> (dz, dbias [N]): dz = dy (y > 0 ? 1 : slope) from the saved output y (None: no activation, dz is dy itself and
+    nothing is copied) and dbias = sum_b dz (out: its destination); None for what is not wanted"""
+    _map_f32("lrelu_bias_bwd", dy, y)
+    slope = _slope("lrelu_bias_bwd", slope)
+    B, N = _map_rows("lrelu_bias_bwd", dy, y)
+    dz = torch.empty_like(dy) if (want_dz and y is not None) else None
+    dbias = _out(out, (N,), dy.device) if want_dbias else None
+    if dz is not None or dbias is not None:
+        _lib.call("sivae_lrelu_bias_bwd", _p(dy), _p(y), slope, _p(dz), _p(dbias), B, N, _s(dy))
+    if want_dz and y is None:
+        dz = dy
+    return dz, dbias
+
+
+def _styles_cfg(who, L, has_s2, cutoff, psi, trunc_cutoff):
+    L = int(L)
+    if L < 1:
+        raise ValueError("sivae_hip.%s: num_layers must be >= 1, got %d" % (who, L))
+    cutoff = L if not has_s2 else int(cutoff)
+    if not 0 <= cutoff <= L:
+        raise ValueError("sivae_hip.%s: the mixing cutoff must be in [0, %d], got %d" % (who, L, cutoff))
+    truncate = psi is not None
+    trunc_cutoff = int(trunc_cutoff) if truncate else 0
+    if not 0 <= trunc_cutoff <= L:
+        raise ValueError("sivae_hip.%s: the truncation cutoff must be in [0, %d], got %d" % (who, L, trunc_cutoff))
+    return L, cutoff, truncate, float(psi) if truncate else 1.0, trunc_cutoff
+
+
+def styles_fwd(s, num_layers, s2=None, cutoff=None, avg=None, beta=None, psi=None, trunc_cutoff=None):
+    """-> styles [B, L, Z] from s [B, Z] (model.py:176-200): with beta, avg [L, Z] <- lerp(avg, mean_b s, 1 - beta) IN
+    PLACE first; with s2, the layers l >= cutoff take s2; with psi, styles[:, l] = lerp(avg[l], styles[:, l], psi) for
+    l < trunc_cutoff"""
+    _map_f32("styles_fwd", s, s2, avg)
+    B, Z = _map_rows("styles_fwd", s, s2)
+    if s2 is not None and cutoff is None:
+        raise ValueError("sivae_hip.styles_fwd: s2 needs the mixing cutoff")
+    if psi is not None and trunc_cutoff is None:
+        raise ValueError("sivae_hip.styles_fwd: psi needs the truncation cutoff")
+    L, cutoff, truncate, psi, trunc_cutoff = _styles_cfg("styles_fwd", num_layers, s2 is not None, cutoff, psi, trunc_cutoff)
+    update = beta is not None
+    if (update or truncate) and avg is None:
+        raise ValueError("sivae_hip.styles_fwd: beta and psi need the running average avg [L, Z]")
+    if avg is not None and tuple(avg.shape) != (L, Z):
+        raise ValueError("sivae_hip.styles_fwd: avg must be [L, Z] = (%d, %d), got %s" % (L, Z, tuple(avg.shape)))
+    weight = 1.0 - float(beta) if update else 0.0  # (formed in double, as the reference's 1.0 - dlatent_avg_beta)
+    if not 0.0 <= weight <= 1.0:
+        raise ValueError("sivae_hip.styles_fwd: beta must be in [0, 1], got %r" % (beta,))
+    out = torch.empty((B, L, Z), dtype=torch.float32, device=s.device)
+    _lib.call("sivae_styles_fwd", _p(s), _p(s2), cutoff, _p(avg), int(update), weight, int(truncate), psi, trunc_cutoff,
+              _p(out), B, L, Z, _s(s))
+    return out
+
+
+def styles_bwd(dstyles, has_s2=False, cutoff=None, psi=None, trunc_cutoff=None, want_ds=True, want_ds2=True):
+    """-> (ds, ds2): the coefficient-weighted sums of dstyles [B, L, Z] over each source's layers; None for what is not
+    wanted (and for ds2 of a forward without s2)"""
+    _map_f32("styles_bwd", dstyles)
+    if dstyles.dim() != 3 or min(dstyles.shape) < 1:
+        raise ValueError("sivae_hip.styles_bwd: expected dstyles [B, L, Z], got %s" % (tuple(dstyles.shape),))
+    B, L, Z = dstyles.shape
+    has_s2 = bool(has_s2)
+    L, cutoff, truncate, psi, trunc_cutoff = _styles_cfg("styles_bwd", L, has_s2, cutoff, psi, trunc_cutoff)
+    ds = torch.empty((B, Z), dtype=torch.float32, device=dstyles.device) if want_ds else None
+    ds2 = torch.empty((B, Z), dtype=torch.float32, device=dstyles.device) if (want_ds2 and has_s2) else None
+    if ds is not None or ds2 is not None:
+        _lib.call("sivae_styles_bwd", _p(dstyles), int(has_s2), cutoff, int(truncate), psi, trunc_cutoff, _p(ds), _p(ds2),
+                  B, L, Z, _s(dstyles))
+    return ds, ds2
+
+
 # ------------------------------------------------------------------------------------------------ multi-tensor launches (multi_tensor.hip)
 def _mt_f32(who, lists):
     """the tensor lists of a multi-tensor call: same length, and per index float32, contiguous, on ONE ROCm device and

@@ -5,6 +5,8 @@ DecodeBlock with
 
     from blocks import Blur, EncodeBlock, DecodeBlock
 
+(or take the whole-file drop-ins next to this one: net.py for the reference's net.py, and model.py, the third drop-in
+file, for its model.py).
 Constructor arguments, forward signatures, state_dict keys (the `blur.weight` buffer included), initial values for a
 seed and the `lr_equalization_coef` attributes the reference's custom_adam.py reads are the reference's; only the
 implicit learning-rate-equalised form (its default) is built.  What follows each convolution runs on sivae_hip.style

@@ -1,16 +1,21 @@
 """Drop-in network classes of the style variant (reference: style_soft_intro_vae/net.py) on the HIP kernels.
 
-Put this directory in front of the reference's style_soft_intro_vae directory on PYTHONPATH: the reference's model.py
-(`from net import *`) and training script then build their encoder, generator and mapping networks from these classes.
+Put this directory in front of the reference's style_soft_intro_vae directory on PYTHONPATH: model.py (`from net import *`;
+the third drop-in file, next to this one and blocks.py, or the reference's own) and the reference's training script then
+build their encoder, generator and mapping networks from these classes.
 Constructor arguments, forward signatures, registry names, state_dict keys and their order, initial values for a seed
 and the `.std` / `lr_equalization_coef` attributes are the reference's; only the implicit learning-rate-equalised form
 (its default) is built, and the DCGAN encoder / generator are not.
 
 What runs where.  The blocks are blocks.py's (fused instance-norm chains, the blur, 3x3 convolutions and linears on the
 HIP kernels).  ToRGB with Generator.decode2's upsample-and-lerp, and FromRGB with the encoders' second LeakyReLU and
-encode2's avg-pool-and-lerp, are one kernel per direction each (sivae_hip.style.to_rgb / from_rgb).  The mapping
-networks' linears run on sivae_hip.functional.linear.  Still torch: pixel_norm, the mapping networks' LeakyReLU, and what
-blocks.py leaves to torch (the fused_scale convolutions of the resolutions from 128 up, upscale2d, downscale2d).
+encode2's avg-pool-and-lerp, are one kernel per direction each (sivae_hip.style.to_rgb / from_rgb).  A mapping network
+is ONE autograd node (sivae_hip.style.mapping): the row pixel-norm kernel, one linear per layer with the LeakyReLU as
+its epilogue, and in the backward one pass per layer for the LeakyReLU and the bias gradient.  Each mapping class has
+`map(x, fused=True)`, which returns the rows [B, N] before the class's view / repeat; `forward` is `map` followed by that
+view / repeat.  `fused=False`, tensors that are not float32 and layer shapes the linear kernels refuse take the per-layer
+chain (torch's pixel_norm and LeakyReLU around sivae_hip.functional.linear).  Still torch: what blocks.py leaves to torch
+(the fused_scale convolutions of the resolutions from 128 up, upscale2d, downscale2d).
 ROCm device tensors only.  An RGB layer with more than 4 image channels, or tensors that are not float32, takes the torch
 chain of the reference instead.
 """
@@ -249,6 +254,13 @@ class MappingBlock(nn.Module):
         return F.leaky_relu(self.fc(x), 0.2)
 
 
+def _run_mapping(x, fcs, normalise, slope, fused):
+    """rows x through the linear layers fcs, each followed by LeakyReLU(slope) (none of them when slope is None): one
+    fused node, or the per-layer chain"""
+    run = style.mapping if fused else style.mapping_chain
+    return run(x, [fc.weight for fc in fcs], [fc.bias for fc in fcs], normalise, slope)
+
+
 def _mapping_widths(mapping_layers, first, hidden, last):
     """(inputs, outputs) of each layer"""
     widths = [first] + [hidden] * (mapping_layers - 1) + [last]
@@ -263,10 +275,13 @@ class Mapping(nn.Module):
         for i, (a, b) in enumerate(_mapping_widths(mapping_layers, latent_size, mapping_fmaps, dlatent_size)):
             setattr(self, "block_%d" % (i + 1), MappingBlock(a, b, lrmul=0.01))
 
+    def map(self, z, fused=True):
+        """the mapped rows [B, dlatent_size], before the repeat over the layers"""
+        fcs = [getattr(self, "block_%d" % (i + 1)).fc for i in range(self.mapping_layers)]
+        return _run_mapping(z, fcs, True, 0.2, fused)
+
     def forward(self, z):
-        x = pixel_norm(z)
-        for i in range(self.mapping_layers):
-            x = getattr(self, "block_%d" % (i + 1))(x)
+        x = self.map(z)
         return x.view(x.shape[0], 1, x.shape[1]).repeat(1, self.num_layers, 1)
 
 
@@ -276,10 +291,13 @@ class _MapBlocks(nn.Module):
         self.mapping_layers = mapping_layers
         self.map_blocks = nn.ModuleList(block(a, b, lrmul=0.1) for a, b in _mapping_widths(mapping_layers, first, hidden, last))
 
-    def _map(self, x):
-        for block in self.map_blocks:
-            x = block(x)
-        return x
+    normalise = False  # pixel_norm in front of the first layer
+    slope = 0.2        # the blocks are MappingBlocks: LeakyReLU(0.2) behind every linear (None: plain linears)
+
+    def map(self, x, fused=True):
+        """the mapped rows [B, N] of x [..., L] flattened to rows, before the class's view / repeat"""
+        fcs = [getattr(block, "fc", block) for block in self.map_blocks]
+        return _run_mapping(x.reshape(-1, x.shape[-1]), fcs, self.normalise, self.slope, fused)
 
 
 @MAPPINGS.register("MappingToLatent")
@@ -287,9 +305,9 @@ class VAEMappingToLatent_old(_MapBlocks):
     def __init__(self, mapping_layers=5, latent_size=256, dlatent_size=256, mapping_fmaps=256):
         super().__init__(mapping_layers, latent_size, mapping_fmaps, 2 * dlatent_size, MappingBlock)
 
-    def forward(self, x):  # ([B, 1, L] from the encoder: the linears flatten it to rows)
-        x = self._map(x)
-        return x.view(x.shape[0], 2, x.shape[2] // 2)
+    def forward(self, x):  # ([B, 1, L] from the encoder: flattened to rows)
+        y = self.map(x)
+        return y.view(x.shape[0], 2, y.shape[1] // 2)
 
 
 @MAPPINGS.register("MappingToLatentNoStyle")
@@ -298,8 +316,11 @@ class VAEMappingToLatentNoStyle(_MapBlocks):
         super().__init__(mapping_layers, latent_size, mapping_fmaps, dlatent_size,
                          lambda a, b, lrmul: _LreqLinear(a, b, lrmul=lrmul))
 
+    slope = None
+
     def forward(self, x):
-        return self._map(x)
+        y = self.map(x)
+        return y.view(*x.shape[:-1], y.shape[1])
 
 
 @MAPPINGS.register("MappingFromLatent")
@@ -308,6 +329,8 @@ class VAEMappingFromLatent(_MapBlocks):
         super().__init__(mapping_layers, dlatent_size, mapping_fmaps, latent_size, MappingBlock)
         self.num_layers = num_layers
 
+    normalise = True
+
     def forward(self, x):
-        x = self._map(pixel_norm(x))
+        x = self.map(x)
         return x.view(x.shape[0], 1, x.shape[1]).repeat(1, self.num_layers, 1)
