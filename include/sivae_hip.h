@@ -1094,6 +1094,18 @@ int sivae_styles_fwd(const float* s, const float* s2, int mix_cutoff, float* avg
 int sivae_styles_bwd(const float* dstyles, int has_s2, int mix_cutoff, int truncate, float psi, int trunc_cutoff, float* ds,
                      float* ds2, int B, int L, int Z, sivae_stream_t stream);
 
+/* ---- the style variant's fused_scale convolutions (scale_conv.hip) --------------------------------------------------------
+ * style_soft_intro_vae/net.py:77,:138 (transform_kernel=True, lreq.py:142-164): stride-2 convolutions over the 4x4 kernel
+ * S(w) summed from four shifted copies of a 3x3 weight.  They are the 3x3 convolution of a nearest-2x upsampled input
+ * ("up") and its adjoint ("down"), which sivae_conv2d_wino_up_fwd / _dgrad / _wgrad and their routes compute, on the weight
+ *   T(w)[o][i][a][b] = w[i][o][2 - a][2 - b].
+ * sivae_conv3x3_flip_transpose is T with a scale, one multiply per element (exact for 1 and 0.25):
+ *   dst[s][r][2 - a][2 - b] = scale * src[r][s][a][b],   src [R][S][3][3], dst [S][R][3][3], src and dst not aliased.
+ * Used both ways: parameter -> effective operand, and effective weight gradient -> the parameter's gradient.  Both
+ * pointers may be any 4-byte-aligned address (SIVAE_ERR_SHAPE otherwise).  SIVAE_ERR_NULL for a missing pointer,
+ * SIVAE_ERR_SHAPE for a non-positive size, SIVAE_ERR_RANGE for 9 R S > 2^31 - 1, all before any launch.  No workspace. */
+int sivae_conv3x3_flip_transpose(const float* src, float* dst, int R, int S, float scale, sivae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -674,6 +674,76 @@ class LinearFn(torch.autograd.Function):
         return dx, _hand(dw, w, k_w), _hand(db, bias, k_b), None
 
 
+# ---- the style variant's fused_scale convolutions ---------------------------------------------------------------------
+# style_soft_intro_vae/net.py:77,:138: stride 2 over the 4x4 kernel summed from four shifted copies of the 3x3 parameter.
+# With T(w)[o][i][a][b] = w[i][o][2 - a][2 - b] they are conv3x3(upsample2(x), T(w)) ("up") and the adjoint of
+# z -> conv3x3(upsample2(z), T(w) / 4) ("down"), so one effective weight E [Cf, Cl, 3, 3] (Cf full-resolution, Cl
+# low-resolution channels) and the three phase-form ops serve both, each op in a different seat:
+#                 forward                           data gradient                      gradient of E
+#     up          conv2d_fwd(x, E, upsample)        conv2d_up_dgrad(dy, E)             conv2d_wgrad(x, dy, upsample)
+#     down        conv2d_up_dgrad(x, E)             conv2d_fwd(dy, E, upsample)        conv2d_wgrad(dy, x, upsample)
+# and the parameter's gradient is scale * T(gradient of E): the same flip-transpose kernel, which is its own adjoint.
+_SCALE = {"up": 1.0, "down": 0.25}
+
+
+class _ScaleW:
+    """the effective weight of one fused_scale parameter and its two PackedW's (operand forms built on first use)"""
+    __slots__ = ("e", "wp0", "wp1")
+
+    def __init__(self, w, kind):
+        self.e = ops.conv3x3_flip_transpose(w.detach(), _SCALE[kind])
+        self.wp0, self.wp1 = ops.PackedW(self.e, 0), ops.PackedW(self.e, 1)
+
+
+def scale_packed(w, kind):
+    """cached ON the parameter under an attribute of its own: `_wtag` drops it after an optimizer step or an in-place
+    edit, and `repack` (which rebuilds the operand forms under `_sivae_pack` from the PARAMETER's storage) never sees it"""
+    return _cached_pack(w, kind, lambda: _ScaleW(w, kind), attr="_sivae_scale_pack")
+
+
+class ScaleConvFn(torch.autograd.Function):
+    """conv_upscale (w [Ci, Co, 3, 3], the transposed convolution's layout) / conv_downscale (w [Co, Ci, 3, 3])"""
+
+    @staticmethod
+    def forward(ctx, x, w, kind):
+        x = x.contiguous()
+        up = kind == "up"
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != w.shape[0 if up else 1]:
+            raise RuntimeError("sivae_hip: conv_%sscale of x %s with weight %s" % (kind, tuple(x.shape), tuple(w.shape)))
+        B, Ci, H, W = x.shape
+        refused = ops.scale_conv_routes(kind, B, Ci, w.shape[1 if up else 0], H, W).refused
+        if refused:
+            raise ValueError("sivae_hip: no kernel route for conv_%sscale of %s: %s" % (kind, tuple(x.shape), refused))
+        _claim(ctx, ((1, w),))
+        ctx.kind = kind
+        ctx.save_for_backward(x, w)
+        sw = scale_packed(w, kind)
+        if up:
+            return ops.conv2d_fwd(x, sw.wp0, w.shape[1], 3, upsample=True)
+        return ops.conv2d_up_dgrad(x, sw.wp0, w.shape[0], wp1=sw.wp1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        k_w, = ctx.use
+        kind = ctx.kind
+        up = kind == "up"
+        dy = dy.contiguous()
+        dw = None
+        if need[1]:
+            de = ops.conv2d_wgrad(x, dy, 3, upsample=True) if up else ops.conv2d_wgrad(dy, x, 3, upsample=True)
+            dw = _hand(ops.conv3x3_flip_transpose(de, _SCALE[kind], out=_dst(w, k_w)), w, k_w)
+        dx = None
+        if need[0]:
+            sw = scale_packed(w, kind)
+            if up:
+                dx = ops.conv2d_up_dgrad(dy, sw.wp0, w.shape[0], wp1=sw.wp1)
+            else:
+                dx = ops.conv2d_fwd(dy, sw.wp0, w.shape[1], 3, upsample=True)
+        return dx, dw, None
+
+
 # ---------------------------------------------------------------------------------------------------
 # sampler / losses
 # ---------------------------------------------------------------------------------------------------
@@ -843,6 +913,17 @@ def conv_bias(x, w, bias, cache=None):
 
 def linear(x, w, bias, relu=False):
     return _apply(LinearFn, x, w, bias, relu)
+
+
+def conv_upscale(x, weight):
+    """F.conv_transpose2d(x, S(weight), stride=2, padding=1) with S the four-shift sum of the 3x3 weight [Ci, Co, 3, 3]:
+    x [B, Ci, H, W] -> [B, Co, 2H, 2W]"""
+    return _apply(ScaleConvFn, x, weight, "up")
+
+
+def conv_downscale(x, weight):
+    """F.conv2d(x, S(weight) / 4, stride=2, padding=1), weight [Co, Ci, 3, 3]: x [B, Ci, H, W] -> [B, Co, H/2, W/2]"""
+    return _apply(ScaleConvFn, x, weight, "down")
 
 
 def reparameterize(mu, logvar, eps):

@@ -570,6 +570,39 @@ def conv2d_up_dgrad_route(B, C, N, H, W, *, has_wp1=False, dx_al8=True):
     return Route("wino_up_dgrad", "sivae_conv2d_wino_up_dgrad", "wino_up_dgrad", "ha", key=key, ratio=_F22_UP)
 
 
+ScaleConvRoutes = collections.namedtuple("ScaleConvRoutes", "forward dgrad wgrad refused")
+
+
+@_memo
+def scale_conv_routes(kind, B, Ci, Co, H, W):
+    """routes of a fused_scale convolution of the style variant (functional.conv_upscale / conv_downscale) on an input
+    [B, Ci, H, W]: kind "up" -> [B, Co, 2H, 2W], "down" -> [B, Co, H/2, W/2].  Both are the 3x3 convolution of a
+    nearest-2x upsampled input with Cl low-resolution and Cf full-resolution channels, run one way or the other:
+        up:    forward conv2d_fwd(upsample)    data gradient conv2d_up_dgrad         weight gradient conv2d_wgrad(upsample)
+        down:  forward conv2d_up_dgrad         data gradient conv2d_fwd(upsample)    weight gradient conv2d_wgrad(upsample)
+    -> (forward, dgrad, wgrad, refused): the three Routes of the layer, and why it stays on torch's convolutions (None:
+    it runs on the kernels)."""
+    if kind not in ("up", "down"):
+        raise ValueError("sivae_hip: scale_conv_routes kind must be 'up' or 'down', got %r" % (kind,))
+    if kind == "down" and (H % 2 or W % 2):
+        return ScaleConvRoutes(None, None, None, "odd full-resolution side %dx%d" % (H, W))
+    (Cl, Cf, h, w) = (Ci, Co, H, W) if kind == "up" else (Co, Ci, H // 2, W // 2)
+    if min(B, Cl, Cf, h, w) <= 0:
+        return ScaleConvRoutes(None, None, None, "empty tensor")
+    conv = conv2d_fwd_route(B, Cl, Cf, 2 * h, 2 * w, 3, upsample=True)
+    # (the destination of the phase data gradient is a tensor of its own here, never a slab view: dx_al8)
+    adj = conv2d_up_dgrad_route(B, Cf, Cl, 2 * h, 2 * w, has_wp1=True)
+    wgrad = conv2d_wgrad_route(B, Cl, Cf, 2 * h, 2 * w, 3, upsample=True)
+    fwd, dgrad = (conv, adj) if kind == "up" else (adj, conv)
+    refused = None
+    for r in (conv, adj, wgrad):
+        if r.error:
+            refused = r.error[1]
+    if refused is None and not conv2d_up_dgrad_supported(h, w):
+        refused = "no phase-form data gradient on %dx%d maps" % (h, w)
+    return ScaleConvRoutes(fwd, dgrad, wgrad, refused)
+
+
 def bn_bwd_route(B, C, H, W, *, op="bn_bwd", four_d=True, dy_pooled=False, nseg=1):
     """route of bn_bwd / bn_bwd_signmask / bn_bwd_dzsum (op: "bn_bwd", "signmask", "dzsum") for x [B, C, H, W] (four_d
     False: x is [B, C] or flat, H * W elements per channel and image): the one-launch persistent kernel, the
@@ -743,6 +776,21 @@ def conv2d_wgrad(x, dy, ks, pro=None, upsample=False, out=None, nseg=1):
     if t0 is not None:  # (includes the tiny slice-reduce launch that follows the MFMA kernel)
         timer_end(t0, r.key, 2.0 * B * H * W * Co * Ci * ks * ks, r.ratio)
     return dw
+
+
+def conv3x3_flip_transpose(w, scale=1.0, out=None):
+    """w [R, S, 3, 3] -> scale * w.transpose(0, 1).flip(2, 3), [S, R, 3, 3] (written into `out` when given: any contiguous
+    float32 view, a parameter-gradient slab among them).  The weight transform of the style variant's fused_scale
+    convolutions and, the other way round, of their weight gradients (scale_conv.hip)."""
+    _require(w, out)
+    if w.dtype != torch.float32:
+        raise TypeError("sivae_hip: expected float32, got %s" % w.dtype)
+    if w.dim() != 4 or w.shape[2] != 3 or w.shape[3] != 3:
+        raise ValueError("sivae_hip: conv3x3_flip_transpose takes a [R, S, 3, 3] weight, got %s" % (tuple(w.shape),))
+    R, S = w.shape[0], w.shape[1]
+    dst = _out(out, (S, R, 3, 3), w.device)
+    _lib.call("sivae_conv3x3_flip_transpose", _p(w), _p(dst), R, S, float(scale), _s(w))
+    return dst
 
 
 # ------------------------------------------------------------------------------------------------ linear

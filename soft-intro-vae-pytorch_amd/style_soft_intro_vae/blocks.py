@@ -11,9 +11,13 @@ Constructor arguments, forward signatures, state_dict keys (the `blur.weight` bu
 seed and the `lr_equalization_coef` attributes the reference's custom_adam.py reads are the reference's; only the
 implicit learning-rate-equalised form (its default) is built.  What follows each convolution runs on sivae_hip.style
 (one fused kernel per chain and direction), the 3x3 stride-1 convolutions on sivae_hip.functional.conv_bias, the linears
-on functional.linear.  Still torch here: the fused_scale=True convolutions (stride 2 with the transformed kernel, the
-resolutions from 128 up), upscale2d and downscale2d.  ROCm device tensors only: there is no CPU path.
+on functional.linear, the fused_scale=True convolutions (stride 2 with the transformed kernel, the resolutions from 128
+up) on functional.conv_upscale / conv_downscale: the phase-form upsample-convolution kernels run one way or the other.
+Still torch here: upscale2d and downscale2d around the fused_scale=False pairs.  ROCm device tensors only: there is no
+CPU path (the convolutions alone still take CPU tensors through torch's).
 """
+import os
+
 import numpy as np
 import torch
 from torch import nn
@@ -21,6 +25,11 @@ from torch.nn import functional as F
 
 from sivae_hip import functional as SF
 from sivae_hip import ops, style
+
+
+# SIVAE_STYLE_SCALE_CONV=0: the fused_scale convolutions stay on torch's stride-2 convolutions (read at call time: tests
+# and tools assign blocks.SCALE_CONV)
+SCALE_CONV = os.environ.get("SIVAE_STYLE_SCALE_CONV", "1") != "0"
 
 
 def pixel_norm(x, epsilon=1e-8):
@@ -62,7 +71,8 @@ class _Linear(nn.Module):
 
 class _Conv3x3(nn.Module):
     """bias-free 3x3 convolution with padding 1.  scale None: stride 1, on the HIP kernels.  'down': stride 2 with the
-    kernel averaged over its four shifts; 'up': the transposed stride-2 form with the summed kernel (both torch)."""
+    kernel averaged over its four shifts; 'up': the transposed stride-2 form with the summed kernel — both on the HIP
+    kernels for float32 device tensors whose shape ops.scale_conv_routes takes, on torch's convolutions otherwise."""
 
     def __init__(self, in_channels, out_channels, scale=None):
         super().__init__()
@@ -77,7 +87,15 @@ class _Conv3x3(nn.Module):
         w = F.pad(self.weight, (1, 1, 1, 1))
         return w[:, :, 1:, 1:] + w[:, :, :-1, 1:] + w[:, :, 1:, :-1] + w[:, :, :-1, :-1]
 
+    def _on_kernels(self, x):
+        if not (SCALE_CONV and x.is_cuda and x.dtype == torch.float32 and self.weight.dtype == torch.float32):
+            return False
+        B, Ci, H, W = x.shape
+        return not ops.scale_conv_routes(self.scale, B, Ci, self.weight.shape[1 if self.scale == "up" else 0], H, W).refused
+
     def forward(self, x):
+        if self.scale is not None and self._on_kernels(x):
+            return SF.conv_upscale(x, self.weight) if self.scale == "up" else SF.conv_downscale(x, self.weight)
         if self.scale == "up":
             return F.conv_transpose2d(x, self._shifted_sum(), None, stride=2, padding=1)
         if self.scale == "down":

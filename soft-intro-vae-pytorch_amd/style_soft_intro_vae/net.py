@@ -14,8 +14,10 @@ is ONE autograd node (sivae_hip.style.mapping): the row pixel-norm kernel, one l
 its epilogue, and in the backward one pass per layer for the LeakyReLU and the bias gradient.  Each mapping class has
 `map(x, fused=True)`, which returns the rows [B, N] before the class's view / repeat; `forward` is `map` followed by that
 view / repeat.  `fused=False`, tensors that are not float32 and layer shapes the linear kernels refuse take the per-layer
-chain (torch's pixel_norm and LeakyReLU around sivae_hip.functional.linear).  Still torch: what blocks.py leaves to torch
-(the fused_scale convolutions of the resolutions from 128 up, upscale2d, downscale2d).
+chain (torch's pixel_norm and LeakyReLU around sivae_hip.functional.linear).  The fused_scale convolutions of the
+resolutions from 128 up run on the phase-form upsample-convolution kernels (blocks._Conv3x3, functional.conv_upscale /
+conv_downscale).  Still torch: what blocks.py leaves to torch (upscale2d and downscale2d around the fused_scale=False
+pairs of the resolutions below 128).
 ROCm device tensors only.  An RGB layer with more than 4 image channels, or tensors that are not float32, takes the torch
 chain of the reference instead.
 """
