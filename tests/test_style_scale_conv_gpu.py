@@ -152,12 +152,12 @@ def test_functions_against_the_reference_form(shape, kind):
         assert e <= K.WINO_TOL, (k, e)
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_the_function_is_the_three_ops(kind):
-    """bit for bit: the effective weight is T(w) (x 1/4 for down) and every result one call of an existing op"""
+def three_ops(kind, shape):
+    """bit for bit: the effective weight is T(w) (x 1/4 for down) and every result one call of an existing op
+    -> (the Function's y, dx, dw; x, gy and the two packs of the effective weight on the device)"""
     from sivae_hip import ops
-    (x, w, gy), _ = case(kind, FIRST)
-    B, Cl, Cf, h, wd = FIRST
+    (x, w, gy), _ = case(kind, shape)
+    B, Cl, Cf, h, wd = shape
     y, dx, dw, _ = run(kind, x, w, gy)
     xg, gyg = put(x), put(gy)
     e = (T(put(w)) * (1.0 if kind == "up" else 0.25)).contiguous()
@@ -174,6 +174,12 @@ def test_the_function_is_the_three_ops(kind):
     assert de.shape == (Cf, Cl, 3, 3)
     assert torch.equal(dw, ops.conv3x3_flip_transpose(de, 1.0 if kind == "up" else 0.25))
     assert torch.equal(dw, T(de) * (1.0 if kind == "up" else 0.25))
+    return (y, dx, dw), (xg, gyg, wp0, wp1)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_function_is_the_three_ops(kind):
+    three_ops(kind, FIRST)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -239,10 +245,9 @@ def test_refused_shapes_take_the_torch_lines(blocks, monkeypatch, kind):
         assert K._err(got[1], want[1]) <= K.WINO_TOL and K._err(got[2], want[2]) <= K.WINO_TOL, tuple(x.shape)
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_taken_shapes_call_no_torch_convolution(blocks, monkeypatch, kind):
-    """the converse: with torch's convolutions patched to fail, forward and backward of a taken row pass"""
-    (x, w, gy), ref = case(kind, FIRST)
+def no_torch_convolution(blocks, monkeypatch, kind, shape, tols=(K.WINO_TOL,) * 3):
+    """with torch's convolutions patched to fail, forward and backward of a taken row pass (tols: of y, dx, dw)"""
+    (x, w, gy), ref = case(kind, shape)
     m = conv_module(blocks, kind, w)
     monkeypatch.setattr(F, "conv_transpose2d", never("F.conv_transpose2d"))
     monkeypatch.setattr(F, "conv2d", never("F.conv2d"))
@@ -250,9 +255,15 @@ def test_taken_shapes_call_no_torch_convolution(blocks, monkeypatch, kind):
     monkeypatch.setattr(torch, "conv_transpose2d", never("torch.conv_transpose2d"))
     got = module_run(m, x, gy)
     monkeypatch.undo()
-    for a, b in zip(got, ref):
-        assert K._err(a, b) <= K.WINO_TOL
+    for a, b, tol in zip(got, ref, tols):
+        assert K._err(a, b) <= tol
     assert "_sivae_scale_pack" in m.weight.__dict__ and "_sivae_pack" not in m.weight.__dict__
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_taken_shapes_call_no_torch_convolution(blocks, monkeypatch, kind):
+    """the converse of the refused shapes"""
+    no_torch_convolution(blocks, monkeypatch, kind, FIRST)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -280,19 +291,25 @@ def test_switch_off_is_todays_lines(blocks, monkeypatch, kind):
 
 
 # ------------------------------------------------------------------------------------------------ the cache
-@pytest.mark.parametrize("kind", KINDS)
-def test_a_stale_effective_weight_would_show(blocks, kind):
+def stale_weight(blocks, kind, shape, tol=K.WINO_TOL, dx_tol=None):
     """the effective weight is cached on the parameter: an in-place edit (version counter), a fused optimizer step and a
-    weight average (both write through raw pointers and bump the generation) each rebuild it"""
+    weight average (both write through raw pointers and bump the generation) each rebuild it.  dx_tol: the data gradient
+    is held to the float64 one of the CURRENT weight after every change as well (where only the backward reads an operand
+    of its own)"""
     from sivae_hip import functional as SF
     from sivae_hip.lreq_adam import LREQAdam, lerp_parameters
-    (x, w, gy), (y_ref, _, _) = case(kind, FIRST)
+    (x, w, gy), (y_ref, _, _) = case(kind, shape)
     m = conv_module(blocks, kind, w)
     p, xg = m.weight, put(x)
 
     def check(y):
-        want = torch_lines(kind, x, p.detach().double().cpu())
-        assert K._err(y, want) <= K.WINO_TOL
+        now = p.detach().double().cpu()
+        want = torch_lines(kind, x, now)
+        assert K._err(y, want) <= tol
+        if dx_tol is not None:
+            _, dx, _ = module_run(m, x, gy)
+            assert K._err(dx, oracle(kind, x, now, gy)[1]) <= dx_tol
+            p.grad = None
         return y.detach().clone()
 
     y0 = check(m(xg))
@@ -315,11 +332,15 @@ def test_a_stale_effective_weight_would_show(blocks, kind):
     assert torch.equal(m(xg), y3)
 
 
-# ------------------------------------------------------------------------------------------------ needs_input_grad
 @pytest.mark.parametrize("kind", KINDS)
-def test_only_wanted_gradients_are_launched(monkeypatch, kind):
+def test_a_stale_effective_weight_would_show(blocks, kind):
+    stale_weight(blocks, kind, FIRST)
+
+
+# ------------------------------------------------------------------------------------------------ needs_input_grad
+def wanted_gradients(monkeypatch, kind, shape):
     from sivae_hip import ops
-    (x, w, gy), (_, dx_ref, dw_ref) = case(kind, FIRST)
+    (x, w, gy), (_, dx_ref, dw_ref) = case(kind, shape)
     full = run(kind, x, w, gy)
     # a frozen weight: no weight gradient, no transform of one
     monkeypatch.setattr(ops, "conv2d_wgrad", never("ops.conv2d_wgrad"))
@@ -338,10 +359,14 @@ def test_only_wanted_gradients_are_launched(monkeypatch, kind):
 
 
 @pytest.mark.parametrize("kind", KINDS)
-def test_gradient_slabs(kind):
+def test_only_wanted_gradients_are_launched(monkeypatch, kind):
+    wanted_gradients(monkeypatch, kind, FIRST)
+
+
+def gradient_slabs(kind, shape):
     """the slot protocol of ConvBiasFn / LinearFn: no slab is claimed under no_grad; a claimed one receives the gradient
     (a view 3 elements into its buffer) and autograd receives None; a use beyond the slabs goes back to autograd"""
-    (x, w, gy), _ = case(kind, FIRST)
+    (x, w, gy), _ = case(kind, shape)
     full = run(kind, x, w, gy)
     wg = torch.nn.Parameter(put(w))
     n = wg.numel()
@@ -364,13 +389,17 @@ def test_gradient_slabs(kind):
     assert torch.equal(wg.grad, full[2])
 
 
+@pytest.mark.parametrize("kind", KINDS)
+def test_gradient_slabs(kind):
+    gradient_slabs(kind, FIRST)
+
+
 # ------------------------------------------------------------------------------------------------ guarded
-@pytest.mark.parametrize("shape", [FIRST, SPLITK], ids=lambda s: "x".join(map(str, s)))
-def test_guarded(shape):
+def guarded_run(shape, kinds=KINDS):
     """forward and backward of both functions on guarded, poisoned outputs and exact workspaces"""
     from sivae_hip import ops
     from support.guard import describe, guarded
-    for kind in KINDS:
+    for kind in kinds:
         (x, w, gy), _ = case(kind, shape)
         base = run(kind, x, w, gy)
         with guarded(ops) as g:
@@ -379,6 +408,11 @@ def test_guarded(shape):
             assert not damage, "guard damage:\n%s" % describe(damage)
         for a, b in zip(got[:3], base[:3]):
             assert bool(torch.isfinite(a).all()) and torch.equal(a, b), (kind, shape)
+
+
+@pytest.mark.parametrize("shape", [FIRST, SPLITK], ids=lambda s: "x".join(map(str, s)))
+def test_guarded(shape):
+    guarded_run(shape)
 
 
 # ------------------------------------------------------------------------------------------------ the blocks
@@ -457,14 +491,14 @@ def test_constructors_give_the_reference_state(fx, blocks, name):
 NET_CFG = dict(startf=2, maxf=8, layer_count=6, latent_size=8)  # 128 x 128: the smallest networks with fused_scale layers
 
 
-def net_run(net, blocks, cls, on, leads):
+def net_run(net, blocks, cls, on, leads, cfg=None, batch=2):
     """forward at lod 5 and the gradients of sum(out g) for every parameter, with blocks.SCALE_CONV = on.  leads: filled
     with the lead term of the generator's decode_block.0.bias_1, whose gradient is exactly 0 (the first layer normalises
     the constant plane, and the noise weights start at 0): measured against the size of the terms of that difference,
     lead = max |r (style + 1)| max |dy| from the layer's own call, as test_style_net_gpu measures it"""
     from sivae_hip import style
     torch.manual_seed(11)
-    m = getattr(net, cls)(**NET_CFG).to(DEV)
+    m = getattr(net, cls)(**(cfg or NET_CFG)).to(DEV)
     g = torch.Generator().manual_seed(12)
     old, style_layer, seen = blocks.SCALE_CONV, style.style_layer, []
 
@@ -480,20 +514,20 @@ def net_run(net, blocks, cls, on, leads):
     try:
         torch.manual_seed(13)  # (the generator's noise draws)
         if cls == "Generator":
-            styles = torch.randn(2, 12, 8, generator=g).to(DEV)
+            styles = torch.randn(batch, 12, 8, generator=g).to(DEV)
             out = m(styles, 5, 1, True)
-            assert out.shape == (2, 3, 128, 128)
+            assert out.shape == (batch, 3, 128, 128)
         else:
-            out = m(torch.randn(2, 3, 128, 128, generator=g).to(DEV), 5, 1)
+            out = m(torch.randn(batch, 3, 128, 128, generator=g).to(DEV), 5, 1)
         (out * torch.randn(out.shape, generator=g).to(DEV)).sum().backward()
     finally:
         blocks.SCALE_CONV, style.style_layer = old, style_layer
     return out.detach(), {k: p.grad for k, p in m.named_parameters()}, m
 
 
-@pytest.mark.parametrize("cls", ["Generator", "Encoder"])
-def test_networks_with_the_switch_on_against_off(blocks, monkeypatch, cls):
-    """the kernels against torch's own stride-2 convolutions inside whole networks (one fused_scale layer each at 128 x 128)"""
+def switch_on_against_off(blocks, monkeypatch, cls, cfg=None, batch=2):
+    """the kernels against torch's own stride-2 convolutions inside whole networks (one fused_scale layer each at 128 x 128)
+    -> the errors it held to the gate, and the module"""
     from sivae_hip import functional as SF
     net = NF.import_net()
     assert net.DecodeBlock is blocks.DecodeBlock  # (one blocks module: the switch below is the one the network reads)
@@ -501,9 +535,9 @@ def test_networks_with_the_switch_on_against_off(blocks, monkeypatch, cls):
     for kind, f in (("up", SF.conv_upscale), ("down", SF.conv_downscale)):
         monkeypatch.setattr(SF, "conv_%sscale" % kind, lambda x, w, f=f, kind=kind: (taken.append(kind), f(x, w))[1])
     leads = {}
-    out_off, g_off, m = net_run(net, blocks, cls, False, leads)
+    out_off, g_off, m = net_run(net, blocks, cls, False, leads, cfg, batch)
     assert taken == [] and (cls == "Generator") == bool(leads)
-    out_on, g_on, _ = net_run(net, blocks, cls, True, {})
+    out_on, g_on, _ = net_run(net, blocks, cls, True, {}, cfg, batch)
     monkeypatch.undo()
     assert taken == ["up" if cls == "Generator" else "down"]
     fused = [b for b in (m.decode_block if cls == "Generator" else m.encode_block) if b.fused_scale]
@@ -518,3 +552,9 @@ def test_networks_with_the_switch_on_against_off(blocks, monkeypatch, cls):
     print("%s 128x128 on against off: output %.2e, gradients worst %.2e (%s; gate %.0e)"
           % (cls, errs["out"], max(errs.values()), max(errs, key=errs.get), TM.CLASS_GRAD_GATE))
     assert max(errs.values()) <= TM.CLASS_GRAD_GATE, errs
+    return errs, fused[0]
+
+
+@pytest.mark.parametrize("cls", ["Generator", "Encoder"])
+def test_networks_with_the_switch_on_against_off(blocks, monkeypatch, cls):
+    switch_on_against_off(blocks, monkeypatch, cls)

@@ -32,6 +32,35 @@ TAKEN = {
     (1, 3, 5, 10, 18): NARROW + ("wino_up_dgrad", 1),
     (1, 128, 128, 8, 16): NARROW + ("wino_up_dgrad_splitk", 2),
 }
+POOL = ("conv_wino_up_kernel<1,4,false>", "conv_wino4_pool_kernel<false>")
+# The routes TAKEN never takes, at 256 CUs (tests/test_style_scale_edges_host.py says what each row is for and holds the two
+# tables to the route functions; tests/test_style_scale_edges_gpu.py runs them): the same layout, then the number of
+# slices of the weight gradient
+EDGE = {
+    (8, 16, 16, 64, 64): POOL + ("wino4_pool", 1, 32),
+    (8, 5, 24, 64, 64): POOL + ("wino4_pool", 1, 32),
+    (8, 64, 16, 64, 64): POOL + ("wino4_pool", 1, 32),
+    (8, 65, 16, 64, 64): WIDE + ("wino_up_dgrad", 1, 32),
+    (7, 16, 16, 64, 64): WIDE + ("wino_up_dgrad", 1, 28),
+    (8, 16, 15, 64, 64): WIDE + ("wino_up_dgrad", 1, 32),
+    (8, 16, 16, 64, 72): WIDE + ("wino_up_dgrad", 1, 40),
+    (8, 3, 65, 64, 64): POOL + ("wino4_pool", 1, 32),
+    (1, 128, 128, 8, 32): WIDE + ("wino_up_dgrad_splitk", 2, 1),
+    (1, 128, 256, 8, 16): NARROW + ("wino_up_dgrad_splitk", 4, 1),
+    (1, 128, 512, 8, 16): NARROW + ("wino_up_dgrad_splitk", 8, 1),
+    (5, 4, 6, 10, 40): WIDE + ("wino_up_dgrad", 1, 2),
+    (1, 3, 5, 9, 18): NARROW + ("wino_up_dgrad", 1, 1),
+    # the remaining combinations of tile, split and slices the closure sweep of the edges file meets
+    (6, 3, 5, 9, 18): NARROW + ("wino_up_dgrad", 1, 2),
+    (4, 65, 128, 10, 40): WIDE + ("wino_up_dgrad_splitk", 2, 2),
+    (1, 65, 256, 10, 40): WIDE + ("wino_up_dgrad_splitk", 4, 1),
+    (4, 65, 256, 10, 40): WIDE + ("wino_up_dgrad_splitk", 4, 2),
+    (1, 65, 512, 10, 40): WIDE + ("wino_up_dgrad_splitk", 8, 1),
+    (4, 65, 512, 10, 40): WIDE + ("wino_up_dgrad_splitk", 8, 2),
+    (16, 65, 128, 8, 16): NARROW + ("wino_up_dgrad_splitk", 2, 2),
+    (16, 65, 256, 8, 16): NARROW + ("wino_up_dgrad_splitk", 4, 2),
+    (16, 65, 512, 8, 16): NARROW + ("wino_up_dgrad_splitk", 8, 2),
+}
 REFUSED = [(2, 3, 5, 4, 6), (1, 4, 4, 5, 7)]
 # configs/ffhq256.yaml (startf 64, maxf 512, 7 layers): kind, Ci, Co, input side
 FFHQ256 = [("up", 256, 128, 64), ("up", 128, 64, 128), ("down", 64, 128, 256), ("down", 128, 256, 128)]
