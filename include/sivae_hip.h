@@ -963,6 +963,37 @@ int sivae_style_enc_bwd(const float* dxn, const float* dmean, const float* dstd,
  * H, W >= 1; y must not overlap x.  The filter is its own adjoint: the same call is the backward (dx from dy).  Rows
  * first, (l + 2 c) + r, then (top + 2 mid) + bottom, times 1 / 16. */
 int sivae_style_blur(const float* x, float* y, int B, int C, int H, int W, sivae_stream_t stream);
+/* The blur folded into the chain next to it: the four entry points below are the ones above with the blurred tensor never
+ * stored.  Arguments, shapes, refusals, the partition of a plane and the order of every sum are those of the plain entry
+ * point, and every output is, bit for bit, what the two calls it replaces give (the stencil is sivae_style_blur's own).
+ *
+ * sivae_style_dec_blur_fwd replaces net.py:49-60 with :166-185 (DecodeBlock.forward: the blur behind conv_1, then the
+ * first layer): sivae_style_dec_fwd of blur(x).  x is the UNBLURRED tensor; the kernel takes the 9 taps from it. */
+int sivae_style_dec_blur_fwd(const float* x, const float* noise, const float* noise_weight, const float* bias,
+                             const float* style, float* y, float* mean, float* rstd, int B, int C, int H, int W, int mode,
+                             int layer, float eps, sivae_stream_t stream);
+/* Its backward from dy, the UNBLURRED x and the forward's mean and rstd: blur(x) is taken by the same 9 taps, the gradient
+ * g with respect to blur(x) is sivae_style_dec_bwd's dx, and dx = blur(g) (the filter is its own adjoint).  dstyle, dbias
+ * and dnoise_weight are sivae_style_dec_bwd's of blur(x).  Where sivae_style_dec_blur_bwd_fused(H, W) is 1 (H W <= 16384,
+ * a plane the kernel stages in 64 KiB of LDS) dx leaves as blur(g): one launch.  Where it is 0, dx receives g and the
+ * caller finishes with sivae_style_blur(dx -> another buffer).  Workspace as sivae_style_dec_bwd's. */
+size_t sivae_style_dec_blur_bwd_workspace_bytes(int B, int C);
+int sivae_style_dec_blur_bwd_fused(int H, int W);
+int sivae_style_dec_blur_bwd(const float* dy, const float* x, const float* noise, const float* noise_weight,
+                             const float* bias, const float* style, const float* mean, const float* rstd, float* dx,
+                             float* dnoise_weight, float* dbias, float* dstyle, int B, int C, int H, int W, int mode,
+                             int layer, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
+/* sivae_style_enc_blur_fwd replaces net.py:94-101 with :110 (EncodeBlock.forward: the first norm, then the blur in front
+ * of conv_2): the outputs are bxn = blur(xn) [B][C][H][W] and sivae_style_enc_fwd's mean and std; xn is not written (a
+ * neighbour's xn is recomputed from x).  Any plane size. */
+int sivae_style_enc_blur_fwd(const float* x, const float* bias, float* bxn, float* mean, float* stddev, int B, int C, int H,
+                             int W, float eps, sivae_stream_t stream);
+/* Its backward: sivae_style_enc_bwd with dxn = blur(dbxn), read from dbxn (which may be NULL) by 9 taps.  dmean, dstd, the
+ * dropped dstd term on a constant plane and the workspace are sivae_style_enc_bwd's.  Any plane size. */
+size_t sivae_style_enc_blur_bwd_workspace_bytes(int B, int C);
+int sivae_style_enc_blur_bwd(const float* dbxn, const float* dmean, const float* dstd, const float* x, const float* bias,
+                             const float* mean, const float* stddev, float* dx, float* dbias, int B, int C, int H, int W,
+                             float eps, void* workspace, size_t workspace_bytes, sivae_stream_t stream);
 
 /* ---- the style variant's RGB layers and the level-of-detail blend (rgb.hip) -------------------------------------------
  * ToRGB and FromRGB of style_soft_intro_vae/net.py with what Generator.decode2 and the encoders' encode2 do around them

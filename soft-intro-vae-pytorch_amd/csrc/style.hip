@@ -12,6 +12,14 @@
 // plane's results depend neither on B, on C, on the other planes nor on the alignment, and two runs are bit-identical.
 // No atomics.  The sums over the batch (dbias, dnoise_weight) go through per-plane fp64 partials in the workspace and a
 // second small launch that adds them in ascending b.
+//
+// The blur in front of a decoder layer and behind an encoder norm is folded into the chains (the *_blur_* kernels, BL):
+// where a chain reads a blurred tensor it takes the 9 taps from the unblurred one in memory (st_blur4: the decoder's x in
+// both directions, the encoder backward's upstream gradient), where it writes one it applies the stencil before the store.
+// The encoder forward recomputes the normalised neighbours from x.  The decoder backward's gradient with respect to
+// blur(x) is made of other threads' registers: planes up to ST_BLUR_LDS_MAX elements are staged in LDS and blurred from
+// there, larger ones are written as they are and the caller runs the blur kernel over them.  The stencil is st_blur9 for all
+// of them and for style_blur_kernel, so a fused chain gives the bits of the two kernels it replaces.
 #include <cmath>
 #include <initializer_list>
 
@@ -25,6 +33,12 @@
 #define ST_SLOPE 0.2f
 #define ST_MAX_HELD_FWD 65536  // elements of the largest plane the forward kernels hold in registers (1024 x 64)
 #define ST_MAX_HELD_BWD 16384  // ... and the backward kernels, which hold two tensors (1024 x 16 each)
+// elements of the largest plane whose gradient the decoder backward with the blur stages in LDS (one launch).  64 KiB of
+// fp32: the static LDS a workgroup may declare, and with it the two 1024-thread blocks a CU holds still fit its 160 KiB,
+// so the staging costs no occupancy.  The reduction scratch shares these bytes (they are never live together).
+#define ST_BLUR_LDS_MAX 16384
+static_assert(ST_BLUR_LDS_MAX <= ST_MAX_HELD_BWD && ST_BLUR_LDS_MAX % 4 == 0 && ST_BLUR_LDS_MAX * 4 <= 65536,
+              "the staged plane is one the backward holds, in whole chunks, within a workgroup's static LDS");
 
 // how the pre-activation is formed from x (block-uniform)
 struct StPre {
@@ -80,11 +94,76 @@ __device__ __forceinline__ void st_chunks(int n, int tid, F&& f) {
   }
 }
 
+// reference: net.py:49-60.  The [1, 2, 1] x [1, 2, 1] / 16 filter at element e = h W + w of a plane [H][W] whose element q
+// is at(q), zeros around the plane: rows first ((l + 2 c) + r), then ((top + 2 mid) + bottom) / 16.
+template <typename I, typename F>
+__device__ __forceinline__ float st_blur9(F&& at, I e, int h, int w, int H, int W) {
+  float rows[3];
+#pragma unroll
+  for (int d = -1; d <= 1; ++d) {
+    float s = 0.f;
+    if (h + d >= 0 && h + d < H) {
+      const I q = e + (I)d * W;
+      const float l = w > 0 ? at(q - 1) : 0.f, rr = w + 1 < W ? at(q + 1) : 0.f;
+      s = (l + 2.f * at(q)) + rr;
+    }
+    rows[d + 1] = s;
+  }
+  return ((rows[0] + 2.f * rows[1]) + rows[2]) * 0.0625f;
+}
+
+// The blurred chunk of 4 elements at i of a plane of n = H W (0 for those at or past n): one division a chunk, its
+// elements are consecutive.  A chunk inside one row (every chunk where W % 4 == 0) takes 6 values a row for its 4
+// elements, the 4 in the middle through at4(q, c) (c[j] = at(q + j)) as ONE 16-byte access where AL and W % 4 == 0 make q a
+// multiple of 4 on a 16-byte aligned plane; each sum is st_blur9's, term for term.  A chunk over a row end goes element
+// by element.
+template <bool AL, typename F, typename F4>
+__device__ __forceinline__ void st_blur4(F&& at, F4&& at4, int i, int n, int H, int W, float (&v)[4]) {
+  int h = i / W, w = i - h * W;
+  if (w + 3 < W) {
+    float rows[3][4];
+#pragma unroll
+    for (int d = -1; d <= 1; ++d) {
+      float(&s)[4] = rows[d + 1];
+      s[0] = s[1] = s[2] = s[3] = 0.f;
+      if (h + d >= 0 && h + d < H) {
+        const int q = i + d * W;
+        float c[4];
+        if (AL && (W & 3) == 0) {
+          at4(q, c);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) c[j] = at(q + j);
+        }
+        const float l = w > 0 ? at(q - 1) : 0.f, rr = w + 4 < W ? at(q + 4) : 0.f;
+        s[0] = (l + 2.f * c[0]) + c[1];
+        s[1] = (c[0] + 2.f * c[1]) + c[2];
+        s[2] = (c[1] + 2.f * c[2]) + c[3];
+        s[3] = (c[2] + 2.f * c[3]) + rr;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = ((rows[0][j] + 2.f * rows[1][j]) + rows[2][j]) * 0.0625f;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[j] = i + j < n ? st_blur9(at, i + j, h, w, H, W) : 0.f;
+    if (++w == W) w = 0, ++h;
+  }
+}
+// ... of a plane in memory (global or LDS)
+template <bool AL>
+__device__ __forceinline__ void st_blur4_of(const float* __restrict__ p, int i, int n, int H, int W, float (&v)[4]) {
+  st_blur4<AL>([&](int q) { return p[q]; }, [&](int q, float(&c)[4]) { st_load4<true>(p, q, n, c); }, i, n, H, W, v);
+}
+
 struct StDecFwdArgs {
   const float *x, *noise, *nw, *bias, *style;
   float *y, *mean, *rstd;
   int C, HW, mode;
   float eps, c1, c2, c3;
+  int H, W;  // (read by the blur forms alone)
 };
 
 __device__ __forceinline__ StPre st_pre(const float* nw, const float* bias, int c, int mode, float c1, float c2, float c3) {
@@ -93,9 +172,9 @@ __device__ __forceinline__ StPre st_pre(const float* nw, const float* bias, int 
   return p;
 }
 
-// reference: net.py:169-185 / :189-205
-template <int NT, int EPT, bool AL>
-__global__ void __launch_bounds__(NT) style_dec_fwd_kernel(StDecFwdArgs a) {
+// reference: net.py:169-185 / :189-205; BL: of blur(x) (net.py:49-60 in front of it, :166-168), read from x by 9 taps
+template <int NT, int EPT, bool AL, bool BL>
+__device__ __forceinline__ void st_dec_fwd(const StDecFwdArgs& a) {
   __shared__ double red[NT / 64];
   constexpr bool HELD = EPT > 0;
   const int plane = blockIdx.x, b = plane / a.C, c = plane - b * a.C, tid = threadIdx.x, n = a.HW;
@@ -107,7 +186,10 @@ __global__ void __launch_bounds__(NT) style_dec_fwd_kernel(StDecFwdArgs a) {
 
   auto load_t = [&](int i, float (&tv)[4]) {
     float xv[4], zv[4] = {0.f, 0.f, 0.f, 0.f};
-    st_load4<AL>(x, i, n, xv);
+    if constexpr (BL)
+      st_blur4_of<AL>(x, i, n, a.H, a.W, xv);
+    else
+      st_load4<AL>(x, i, n, xv);
     if (p.mode) st_load4<AL>(nz, i, n, zv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) tv[j] = st_dec_t(xv[j], zv[j], p);
@@ -146,6 +228,14 @@ __global__ void __launch_bounds__(NT) style_dec_fwd_kernel(StDecFwdArgs a) {
   });
   if (tid == 0) a.mean[plane] = m, a.rstd[plane] = r;
 }
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_dec_fwd_kernel(StDecFwdArgs a) {
+  st_dec_fwd<NT, EPT, AL, false>(a);
+}
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_dec_blur_fwd_kernel(StDecFwdArgs a) {
+  st_dec_fwd<NT, EPT, AL, true>(a);
+}
 
 struct StDecBwdArgs {
   const float *dy, *x, *noise, *nw, *bias, *style, *mean, *rstd;
@@ -153,12 +243,19 @@ struct StDecBwdArgs {
   double* part;  // [2][B C]: sum dp, sum dp noise per plane (null: neither dbias nor dnoise_weight is wanted)
   int C, HW, mode, planes;
   float c1, c2, c3;
+  int H, W, stage;  // (the blur forms alone; stage: H W <= ST_BLUR_LDS_MAX, dx leaves blurred)
 };
 
-template <int NT, int EPT, bool AL>
-__global__ void __launch_bounds__(NT) style_dec_bwd_kernel(StDecBwdArgs a) {
-  __shared__ double red[2 * NT / 64];
+// BL: x is the UNBLURRED input, the layer's is blur(x) by 9 taps; the gradient with respect to blur(x) is formed as the
+// plain form's dx and, where the plane is staged (a held plane up to ST_BLUR_LDS_MAX), blurred from LDS before the store
+template <int NT, int EPT, bool AL, bool BL>
+__device__ __forceinline__ void st_dec_bwd(const StDecBwdArgs& a) {
   constexpr bool HELD = EPT > 0;
+  constexpr int STAGE = BL && HELD ? (NT * EPT < ST_BLUR_LDS_MAX ? NT * EPT : ST_BLUR_LDS_MAX) : 0;  // staged floats
+  constexpr int RED = 2 * NT / 64;
+  __shared__ __align__(16) double smem[RED > STAGE / 2 ? RED : STAGE / 2];
+  double* red = smem;
+  float* stage = reinterpret_cast<float*>(smem);  // (same bytes: separated from red's use by barriers)
   const int plane = blockIdx.x, b = plane / a.C, c = plane - b * a.C, tid = threadIdx.x, n = a.HW;
   const float* x = a.x + (size_t)plane * n;
   const float* dy = a.dy + (size_t)plane * n;
@@ -167,11 +264,18 @@ __global__ void __launch_bounds__(NT) style_dec_bwd_kernel(StDecBwdArgs a) {
   const float m = a.mean[plane], r = a.rstd[plane];
   float xs[HELD ? EPT : 4], gs[HELD ? EPT : 4];
 
+  auto load_x = [&](int i, float (&xv)[4]) {
+    if constexpr (BL)
+      st_blur4_of<AL>(x, i, n, a.H, a.W, xv);
+    else
+      st_load4<AL>(x, i, n, xv);
+  };
+
   // sum dy and sum dy xh (a chunk's elements past n load as zero gradients)
   float s1 = 0.f, s2 = 0.f;
   st_chunks<NT, EPT>(n, tid, [&](int k, int i) {
     float xv[4], gv[4], zv[4] = {0.f, 0.f, 0.f, 0.f};
-    st_load4<AL>(x, i, n, xv);
+    load_x(i, xv);
     st_load4<AL>(dy, i, n, gv);
     if (p.mode) st_load4<AL>(nz, i, n, zv);
 #pragma unroll
@@ -192,11 +296,13 @@ __global__ void __launch_bounds__(NT) style_dec_bwd_kernel(StDecBwdArgs a) {
   const float k1 = (float)(S1 / (double)n), k2 = (float)(S2 / (double)n);
   const float g = r * (a.style[(size_t)b * 2 * a.C + c] + 1.f);
   float* dx = a.dx ? a.dx + (size_t)plane * n : nullptr;
+  const bool staged = STAGE > 0 && a.stage && dx;  // (block-uniform)
+  if (staged) __syncthreads();                     // (every thread has read red: its bytes take the plane now)
   float p1 = 0.f, p2 = 0.f;
   st_chunks<NT, EPT>(n, tid, [&](int k, int i) {
     float xv[4], gv[4], zv[4] = {0.f, 0.f, 0.f, 0.f}, ov[4];
     if (!HELD) {
-      st_load4<AL>(x, i, n, xv);
+      load_x(i, xv);
       st_load4<AL>(dy, i, n, gv);
     }
     if (p.mode) st_load4<AL>(nz, i, n, zv);  // (one plane per sample at the most: re-read from cache, not held)
@@ -211,13 +317,32 @@ __global__ void __launch_bounds__(NT) style_dec_bwd_kernel(StDecBwdArgs a) {
       p2 += dp * zv[j];
       ov[j] = p.mode ? dp : dp * (1.f + p.c3 * xe * expf(p.c2 * xe * xe));
     }
-    if (dx) st_store4<AL>(dx, i, n, ov);
+    if (staged)
+      st_store4<AL>(stage, i, n, ov);
+    else if (dx)
+      st_store4<AL>(dx, i, n, ov);
   });
+  if (staged) {
+    __syncthreads();
+    st_chunks<NT, EPT>(n, tid, [&](int, int i) {
+      float ov[4];
+      st_blur4_of<AL>(stage, i, n, a.H, a.W, ov);
+      st_store4<AL>(dx, i, n, ov);
+    });
+  }
   if (a.part) {
     double P1 = (double)p1, P2 = (double)p2;
-    block_sum2<NT>(P1, P2, red);
+    block_sum2<NT>(P1, P2, red);  // (its first barrier is behind every thread's reads of the staged plane)
     if (tid == 0) a.part[plane] = P1, a.part[a.planes + plane] = P2;
   }
+}
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_dec_bwd_kernel(StDecBwdArgs a) {
+  st_dec_bwd<NT, EPT, AL, false>(a);
+}
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_dec_blur_bwd_kernel(StDecBwdArgs a) {
+  st_dec_bwd<NT, EPT, AL, true>(a);
 }
 
 // out0[c] = sum_b part[b C + c], out1[c] = sum_b part[B C + b C + c], b ascending (either output may be null)
@@ -239,11 +364,12 @@ struct StEncFwdArgs {
   float *xn, *mean, *std;
   int C, HW;
   float eps;
+  int H, W;  // (read by the blur form alone)
 };
 
-// reference: net.py:94-101 / :113-121
-template <int NT, int EPT, bool AL>
-__global__ void __launch_bounds__(NT) style_enc_fwd_kernel(StEncFwdArgs a) {
+// reference: net.py:94-101 / :113-121; BL: xn leaves as blur(xn) (net.py:110), the neighbours' xn recomputed from x
+template <int NT, int EPT, bool AL, bool BL>
+__device__ __forceinline__ void st_enc_fwd(const StEncFwdArgs& a) {
   __shared__ double red[NT / 64];
   constexpr bool HELD = EPT > 0;
   const int plane = blockIdx.x, c = plane % a.C, tid = threadIdx.x, n = a.HW;
@@ -283,12 +409,30 @@ __global__ void __launch_bounds__(NT) style_enc_fwd_kernel(StEncFwdArgs a) {
   const float r = (float)(1.0 / sqrt(v + (double)a.eps));
   st_chunks<NT, EPT>(n, tid, [&](int k, int i) {
     float tv[4], yv[4];
-    if (!HELD) load_t(i, tv);
+    if constexpr (BL) {
+      auto xn_at = [&](int q) { return (st_lrelu(x[q] + bias) - m) * r; };  // (the expression the plain form stores)
+      auto xn_at4 = [&](int q, float(&c)[4]) {
+        st_load4<true>(x, q, n, c);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) yv[j] = ((HELD ? t[4 * k + j] : tv[j]) - m) * r;
+        for (int j = 0; j < 4; ++j) c[j] = (st_lrelu(c[j] + bias) - m) * r;
+      };
+      st_blur4<AL>(xn_at, xn_at4, i, n, a.H, a.W, yv);
+    } else {
+      if (!HELD) load_t(i, tv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) yv[j] = ((HELD ? t[4 * k + j] : tv[j]) - m) * r;
+    }
     st_store4<AL>(xn, i, n, yv);
   });
   if (tid == 0) a.mean[plane] = m, a.std[plane] = (float)sqrt(v);
+}
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_enc_fwd_kernel(StEncFwdArgs a) {
+  st_enc_fwd<NT, EPT, AL, false>(a);
+}
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_enc_blur_fwd_kernel(StEncFwdArgs a) {
+  st_enc_fwd<NT, EPT, AL, true>(a);
 }
 
 struct StEncBwdArgs {
@@ -297,10 +441,12 @@ struct StEncBwdArgs {
   double* part;  // [B C]: sum dp per plane (null: dbias is not wanted)
   int C, HW;
   float eps;
+  int H, W;  // (read by the blur form alone)
 };
 
-template <int NT, int EPT, bool AL>
-__global__ void __launch_bounds__(NT) style_enc_bwd_kernel(StEncBwdArgs a) {
+// BL: dxn is the gradient of blur(xn); xn's is its blur (the filter is its own adjoint), read from it by 9 taps
+template <int NT, int EPT, bool AL, bool BL>
+__device__ __forceinline__ void st_enc_bwd(const StEncBwdArgs& a) {
   __shared__ double red[2 * NT / 64];
   constexpr bool HELD = EPT > 0;
   const int plane = blockIdx.x, c = plane % a.C, tid = threadIdx.x, n = a.HW;
@@ -310,12 +456,19 @@ __global__ void __launch_bounds__(NT) style_enc_bwd_kernel(StEncBwdArgs a) {
   const float r = (float)(1.0 / sqrt((double)sd * (double)sd + (double)a.eps));
   float xs[HELD ? EPT : 4], gs[HELD ? EPT : 4];
 
+  auto load_g = [&](int i, float (&gv)[4]) {
+    if constexpr (BL)
+      st_blur4_of<AL>(dxn, i, n, a.H, a.W, gv);
+    else
+      st_load4<AL>(dxn, i, n, gv);
+  };
+
   float s1 = 0.f, s2 = 0.f;
   if (HELD || dxn) {
     st_chunks<NT, EPT>(n, tid, [&](int k, int i) {
       float xv[4], gv[4] = {0.f, 0.f, 0.f, 0.f};
       st_load4<AL>(x, i, n, xv);
-      if (dxn) st_load4<AL>(dxn, i, n, gv);
+      if (dxn) load_g(i, gv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (HELD) xs[4 * k + j] = xv[j], gs[4 * k + j] = gv[j];
@@ -336,7 +489,7 @@ __global__ void __launch_bounds__(NT) style_enc_bwd_kernel(StEncBwdArgs a) {
     float xv[4], gv[4] = {0.f, 0.f, 0.f, 0.f}, ov[4];
     if (!HELD) {
       st_load4<AL>(x, i, n, xv);
-      if (dxn) st_load4<AL>(dxn, i, n, gv);
+      if (dxn) load_g(i, gv);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -355,25 +508,23 @@ __global__ void __launch_bounds__(NT) style_enc_bwd_kernel(StEncBwdArgs a) {
     if (tid == 0) a.part[plane] = P1;
   }
 }
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_enc_bwd_kernel(StEncBwdArgs a) {
+  st_enc_bwd<NT, EPT, AL, false>(a);
+}
+template <int NT, int EPT, bool AL>
+__global__ void __launch_bounds__(NT) style_enc_blur_bwd_kernel(StEncBwdArgs a) {
+  st_enc_bwd<NT, EPT, AL, true>(a);
+}
 
-// reference: net.py:49-60.  One thread per output element; rows first ((l + 2 c) + r), then ((top + 2 mid) + bottom) / 16.
+// reference: net.py:49-60.  One thread per output element (st_blur9 around it; the taps are offsets from the element).
 __global__ void __launch_bounds__(256) style_blur_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total,
                                                          int H, int W) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
   const int w = (int)(e % W), h = (int)((e / W) % H);
-  float rows[3];
-#pragma unroll
-  for (int d = -1; d <= 1; ++d) {
-    float s = 0.f;
-    if (h + d >= 0 && h + d < H) {
-      const float* p = x + ((ptrdiff_t)e + (ptrdiff_t)d * W);
-      const float l = w > 0 ? p[-1] : 0.f, rr = w + 1 < W ? p[1] : 0.f;
-      s = (l + 2.f * p[0]) + rr;
-    }
-    rows[d + 1] = s;
-  }
-  y[e] = ((rows[0] + 2.f * rows[1]) + rows[2]) * 0.0625f;
+  const float* p = x + e;
+  y[e] = st_blur9([&](ptrdiff_t q) { return p[q]; }, (ptrdiff_t)0, h, w, H, W);
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
@@ -429,9 +580,10 @@ static void st_mode0_consts(int layer, float* c1, float* c2, float* c3) {
     else ST_LAUNCH(KERN, 1024, 0, al, planes, stream, args);                       \
   } while (0)
 
-extern "C" int sivae_style_dec_fwd(const float* x, const float* noise, const float* noise_weight, const float* bias,
-                                   const float* style, float* y, float* mean, float* rstd, int B, int C, int H, int W,
-                                   int mode, int layer, float eps, hipStream_t stream) {
+// Each entry point and its *_blur_* twin share one host function: the same validation, the kernel chosen by `blur`.
+static int st_dec_fwd_host(bool blur, const float* x, const float* noise, const float* noise_weight, const float* bias,
+                           const float* style, float* y, float* mean, float* rstd, int B, int C, int H, int W, int mode,
+                           int layer, float eps, hipStream_t stream) {
   if (!x || !bias || !style || !y || !mean || !rstd) return SIVAE_ERR_NULL;
   if (mode < 0 || mode > 2) return SIVAE_ERR_MODE;
   if (mode != 0 && (!noise || !noise_weight)) return SIVAE_ERR_NULL;
@@ -440,21 +592,41 @@ extern "C" int sivae_style_dec_fwd(const float* x, const float* noise, const flo
   if (layer < 0 || !(eps >= 0.f)) return SIVAE_ERR_SHAPE;
   if (!st_al4({x, noise, noise_weight, bias, style, y, mean, rstd})) return SIVAE_ERR_SHAPE;
   const int HW = H * W;
-  StDecFwdArgs a = {x, mode ? noise : nullptr, noise_weight, bias, style, y, mean, rstd, C, HW, mode, eps, 0.f, 0.f, 0.f};
+  StDecFwdArgs a = {x, mode ? noise : nullptr, noise_weight, bias, style, y, mean, rstd, C, HW, mode, eps, 0.f, 0.f, 0.f,
+                    H, W};
   st_mode0_consts(layer, &a.c1, &a.c2, &a.c3);
   const bool al = st_al16(HW, {x, a.noise, y});
-  ST_DISPATCH_FWD(style_dec_fwd_kernel, HW, al, (long long)B * C, stream, a);
+  if (blur)
+    ST_DISPATCH_FWD(style_dec_blur_fwd_kernel, HW, al, (long long)B * C, stream, a);
+  else
+    ST_DISPATCH_FWD(style_dec_fwd_kernel, HW, al, (long long)B * C, stream, a);
   return sivae_launch_status();
+}
+
+extern "C" int sivae_style_dec_fwd(const float* x, const float* noise, const float* noise_weight, const float* bias,
+                                   const float* style, float* y, float* mean, float* rstd, int B, int C, int H, int W,
+                                   int mode, int layer, float eps, hipStream_t stream) {
+  return st_dec_fwd_host(false, x, noise, noise_weight, bias, style, y, mean, rstd, B, C, H, W, mode, layer, eps, stream);
+}
+extern "C" int sivae_style_dec_blur_fwd(const float* x, const float* noise, const float* noise_weight, const float* bias,
+                                        const float* style, float* y, float* mean, float* rstd, int B, int C, int H, int W,
+                                        int mode, int layer, float eps, hipStream_t stream) {
+  return st_dec_fwd_host(true, x, noise, noise_weight, bias, style, y, mean, rstd, B, C, H, W, mode, layer, eps, stream);
 }
 
 extern "C" size_t sivae_style_dec_bwd_workspace_bytes(int B, int C) {
   return B > 0 && C > 0 ? 2 * (size_t)B * (size_t)C * sizeof(double) : 0;
 }
+extern "C" size_t sivae_style_dec_blur_bwd_workspace_bytes(int B, int C) { return sivae_style_dec_bwd_workspace_bytes(B, C); }
 
-extern "C" int sivae_style_dec_bwd(const float* dy, const float* x, const float* noise, const float* noise_weight,
-                                   const float* bias, const float* style, const float* mean, const float* rstd, float* dx,
-                                   float* dnoise_weight, float* dbias, float* dstyle, int B, int C, int H, int W, int mode,
-                                   int layer, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+extern "C" int sivae_style_dec_blur_bwd_fused(int H, int W) {
+  return H > 0 && W > 0 && (long long)H * W <= ST_BLUR_LDS_MAX ? 1 : 0;
+}
+
+static int st_dec_bwd_host(bool blur, const float* dy, const float* x, const float* noise, const float* noise_weight,
+                           const float* bias, const float* style, const float* mean, const float* rstd, float* dx,
+                           float* dnoise_weight, float* dbias, float* dstyle, int B, int C, int H, int W, int mode, int layer,
+                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!dy || !x || !bias || !style || !mean || !rstd) return SIVAE_ERR_NULL;
   if (mode < 0 || mode > 2) return SIVAE_ERR_MODE;
   if (mode != 0 && (!noise || !noise_weight)) return SIVAE_ERR_NULL;
@@ -470,37 +642,70 @@ extern "C" int sivae_style_dec_bwd(const float* dy, const float* x, const float*
   if (!dx && !sums && !dstyle) return SIVAE_OK;
   const int HW = H * W;
   StDecBwdArgs a = {dy, x, mode ? noise : nullptr, noise_weight, bias, style, mean, rstd, dx, dstyle,
-                    sums ? static_cast<double*>(workspace) : nullptr, C, HW, mode, B * C, 0.f, 0.f, 0.f};
+                    sums ? static_cast<double*>(workspace) : nullptr, C, HW, mode, B * C, 0.f, 0.f, 0.f,
+                    H, W, sivae_style_dec_blur_bwd_fused(H, W)};
   st_mode0_consts(layer, &a.c1, &a.c2, &a.c3);
   const bool al = st_al16(HW, {dy, x, a.noise, dx});
-  ST_DISPATCH_BWD(style_dec_bwd_kernel, HW, al, (long long)B * C, stream, a);
+  if (blur)
+    ST_DISPATCH_BWD(style_dec_blur_bwd_kernel, HW, al, (long long)B * C, stream, a);
+  else
+    ST_DISPATCH_BWD(style_dec_bwd_kernel, HW, al, (long long)B * C, stream, a);
   if (sums)
     hipLaunchKernelGGL(style_batch_sum_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, stream, a.part, dbias,
                        dnoise_weight, B, C);
   return sivae_launch_status();
 }
 
-extern "C" int sivae_style_enc_fwd(const float* x, const float* bias, float* xn, float* mean, float* stddev, int B, int C,
-                                   int H, int W, float eps, hipStream_t stream) {
+extern "C" int sivae_style_dec_bwd(const float* dy, const float* x, const float* noise, const float* noise_weight,
+                                   const float* bias, const float* style, const float* mean, const float* rstd, float* dx,
+                                   float* dnoise_weight, float* dbias, float* dstyle, int B, int C, int H, int W, int mode,
+                                   int layer, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return st_dec_bwd_host(false, dy, x, noise, noise_weight, bias, style, mean, rstd, dx, dnoise_weight, dbias, dstyle, B, C,
+                         H, W, mode, layer, workspace, workspace_bytes, stream);
+}
+extern "C" int sivae_style_dec_blur_bwd(const float* dy, const float* x, const float* noise, const float* noise_weight,
+                                        const float* bias, const float* style, const float* mean, const float* rstd,
+                                        float* dx, float* dnoise_weight, float* dbias, float* dstyle, int B, int C, int H,
+                                        int W, int mode, int layer, void* workspace, size_t workspace_bytes,
+                                        hipStream_t stream) {
+  return st_dec_bwd_host(true, dy, x, noise, noise_weight, bias, style, mean, rstd, dx, dnoise_weight, dbias, dstyle, B, C,
+                         H, W, mode, layer, workspace, workspace_bytes, stream);
+}
+
+static int st_enc_fwd_host(bool blur, const float* x, const float* bias, float* xn, float* mean, float* stddev, int B, int C,
+                           int H, int W, float eps, hipStream_t stream) {
   if (!x || !bias || !xn || !mean || !stddev) return SIVAE_ERR_NULL;
   const int rc = st_check_shape(B, C, H, W);
   if (rc != SIVAE_OK) return rc;
   if (!(eps >= 0.f)) return SIVAE_ERR_SHAPE;
   if (!st_al4({x, bias, xn, mean, stddev})) return SIVAE_ERR_SHAPE;
   const int HW = H * W;
-  const StEncFwdArgs a = {x, bias, xn, mean, stddev, C, HW, eps};
+  const StEncFwdArgs a = {x, bias, xn, mean, stddev, C, HW, eps, H, W};
   const bool al = st_al16(HW, {x, xn});
-  ST_DISPATCH_FWD(style_enc_fwd_kernel, HW, al, (long long)B * C, stream, a);
+  if (blur)
+    ST_DISPATCH_FWD(style_enc_blur_fwd_kernel, HW, al, (long long)B * C, stream, a);
+  else
+    ST_DISPATCH_FWD(style_enc_fwd_kernel, HW, al, (long long)B * C, stream, a);
   return sivae_launch_status();
+}
+
+extern "C" int sivae_style_enc_fwd(const float* x, const float* bias, float* xn, float* mean, float* stddev, int B, int C,
+                                   int H, int W, float eps, hipStream_t stream) {
+  return st_enc_fwd_host(false, x, bias, xn, mean, stddev, B, C, H, W, eps, stream);
+}
+extern "C" int sivae_style_enc_blur_fwd(const float* x, const float* bias, float* bxn, float* mean, float* stddev, int B,
+                                        int C, int H, int W, float eps, hipStream_t stream) {
+  return st_enc_fwd_host(true, x, bias, bxn, mean, stddev, B, C, H, W, eps, stream);
 }
 
 extern "C" size_t sivae_style_enc_bwd_workspace_bytes(int B, int C) {
   return B > 0 && C > 0 ? (size_t)B * (size_t)C * sizeof(double) : 0;
 }
+extern "C" size_t sivae_style_enc_blur_bwd_workspace_bytes(int B, int C) { return sivae_style_enc_bwd_workspace_bytes(B, C); }
 
-extern "C" int sivae_style_enc_bwd(const float* dxn, const float* dmean, const float* dstd, const float* x, const float* bias,
-                                   const float* mean, const float* stddev, float* dx, float* dbias, int B, int C, int H,
-                                   int W, float eps, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+static int st_enc_bwd_host(bool blur, const float* dxn, const float* dmean, const float* dstd, const float* x,
+                           const float* bias, const float* mean, const float* stddev, float* dx, float* dbias, int B, int C,
+                           int H, int W, float eps, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!x || !bias || !mean || !stddev) return SIVAE_ERR_NULL;
   const int rc = st_check_shape(B, C, H, W);
   if (rc != SIVAE_OK) return rc;
@@ -511,13 +716,30 @@ extern "C" int sivae_style_enc_bwd(const float* dxn, const float* dmean, const f
   if (!dx && !dbias) return SIVAE_OK;
   const int HW = H * W;
   const StEncBwdArgs a = {dxn, dmean, dstd, x, bias, mean, stddev, dx, dbias ? static_cast<double*>(workspace) : nullptr,
-                          C, HW, eps};
+                          C, HW, eps, H, W};
   const bool al = st_al16(HW, {dxn, x, dx});
-  ST_DISPATCH_BWD(style_enc_bwd_kernel, HW, al, (long long)B * C, stream, a);
+  if (blur)
+    ST_DISPATCH_BWD(style_enc_blur_bwd_kernel, HW, al, (long long)B * C, stream, a);
+  else
+    ST_DISPATCH_BWD(style_enc_bwd_kernel, HW, al, (long long)B * C, stream, a);
   if (dbias)
     hipLaunchKernelGGL(style_batch_sum_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, stream, a.part, dbias,
                        static_cast<float*>(nullptr), B, C);
   return sivae_launch_status();
+}
+
+extern "C" int sivae_style_enc_bwd(const float* dxn, const float* dmean, const float* dstd, const float* x, const float* bias,
+                                   const float* mean, const float* stddev, float* dx, float* dbias, int B, int C, int H,
+                                   int W, float eps, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return st_enc_bwd_host(false, dxn, dmean, dstd, x, bias, mean, stddev, dx, dbias, B, C, H, W, eps, workspace,
+                         workspace_bytes, stream);
+}
+extern "C" int sivae_style_enc_blur_bwd(const float* dbxn, const float* dmean, const float* dstd, const float* x,
+                                        const float* bias, const float* mean, const float* stddev, float* dx, float* dbias,
+                                        int B, int C, int H, int W, float eps, void* workspace, size_t workspace_bytes,
+                                        hipStream_t stream) {
+  return st_enc_bwd_host(true, dbxn, dmean, dstd, x, bias, mean, stddev, dx, dbias, B, C, H, W, eps, workspace,
+                         workspace_bytes, stream);
 }
 
 extern "C" int sivae_style_blur(const float* x, float* y, int B, int C, int H, int W, hipStream_t stream) {

@@ -1613,9 +1613,10 @@ def _style_dims(who, x, bias, style=None, noise=None, noise_weight=None, mode=0)
     return B, C, H, W
 
 
-def style_dec_fwd(x, noise, noise_weight, bias, style, mode, layer=0, eps=1e-8):
+def style_dec_fwd(x, noise, noise_weight, bias, style, mode, layer=0, eps=1e-8, blur=False):
     """-> (y, mean [B, C], rstd [B, C]): noise injection (mode 1: noise [B, 1, H, W]; 2: [1, 1, H, W]; 0: none, the
-    layer's fixed bump) -> bias -> LeakyReLU(0.2) -> InstanceNorm -> y = xh (style[:, :C] + 1) + style[:, C:]"""
+    layer's fixed bump) -> bias -> LeakyReLU(0.2) -> InstanceNorm -> y = xh (style[:, :C] + 1) + style[:, C:].
+    blur=True: the same of style_blur(x), bit for bit, taken from x by 9 taps (the blurred tensor is never stored)"""
     if mode == STYLE_NOISE_NONE:
         noise = noise_weight = None
     _style_f32("style_dec_fwd", x, noise, noise_weight, bias, style)
@@ -1624,17 +1625,19 @@ def style_dec_fwd(x, noise, noise_weight, bias, style, mode, layer=0, eps=1e-8):
     mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
     rstd = torch.empty((B, C), dtype=torch.float32, device=x.device)
     t0 = timer_begin()
-    _lib.call("sivae_style_dec_fwd", _p(x), _p(noise), _p(noise_weight), _p(bias), _p(style), _p(y), _p(mean), _p(rstd),
-              B, C, H, W, int(mode), int(layer), float(eps), _s(x))
+    _lib.call("sivae_style_dec_blur_fwd" if blur else "sivae_style_dec_fwd", _p(x), _p(noise), _p(noise_weight), _p(bias),
+              _p(style), _p(y), _p(mean), _p(rstd), B, C, H, W, int(mode), int(layer), float(eps), _s(x))
     if t0 is not None:
-        timer_end(t0, "style_dec_fwd_kernel", 12.0 * x.numel())
+        timer_end(t0, "style_dec_blur_fwd_kernel" if blur else "style_dec_fwd_kernel", 12.0 * x.numel())
     return y, mean, rstd
 
 
 def style_dec_bwd(dy, x, noise, noise_weight, bias, style, mean, rstd, mode, layer=0, want_dx=True, want_dnw=True,
-                  want_dbias=True, want_dstyle=True):
+                  want_dbias=True, want_dstyle=True, blur=False):
     """-> (dx, dnoise_weight [C], dbias [C], dstyle [B, 2 C]), None for what is not wanted (and for dnoise_weight in mode
-    0); the activation is recomputed from x"""
+    0); the activation is recomputed from x.  blur=True: the backward of style_dec_fwd(..., blur=True) from the UNBLURRED
+    x, dx = style_blur of the gradient with respect to style_blur(x): inside the kernel where style_dec_blur_bwd_fused(H, W)
+    says so, by a style_blur call here otherwise"""
     if mode == STYLE_NOISE_NONE:
         noise = noise_weight = None
         want_dnw = False
@@ -1646,33 +1649,45 @@ def style_dec_bwd(dy, x, noise, noise_weight, bias, style, mean, rstd, mode, lay
     dnw = torch.empty(C, dtype=torch.float32, device=x.device) if want_dnw else None
     dbias = torch.empty(C, dtype=torch.float32, device=x.device) if want_dbias else None
     dstyle = torch.empty((B, 2 * C), dtype=torch.float32, device=x.device) if want_dstyle else None
-    ws = workspace(_lib.load().sivae_style_dec_bwd_workspace_bytes(B, C), x.device) if (want_dnw or want_dbias) else None
+    L = _lib.load()
+    ws_bytes = (L.sivae_style_dec_blur_bwd_workspace_bytes if blur else L.sivae_style_dec_bwd_workspace_bytes)(B, C)
+    ws = workspace(ws_bytes, x.device) if (want_dnw or want_dbias) else None
     t0 = timer_begin()
-    _lib.call("sivae_style_dec_bwd", _p(dy), _p(x), _p(noise), _p(noise_weight), _p(bias), _p(style), _p(mean), _p(rstd),
-              _p(dx), _p(dnw), _p(dbias), _p(dstyle), B, C, H, W, int(mode), int(layer), _p(ws),
-              0 if ws is None else ws.numel(), _s(x))
+    _lib.call("sivae_style_dec_blur_bwd" if blur else "sivae_style_dec_bwd", _p(dy), _p(x), _p(noise), _p(noise_weight),
+              _p(bias), _p(style), _p(mean), _p(rstd), _p(dx), _p(dnw), _p(dbias), _p(dstyle), B, C, H, W, int(mode),
+              int(layer), _p(ws), 0 if ws is None else ws.numel(), _s(x))
     if t0 is not None:
-        timer_end(t0, "style_dec_bwd_kernel", 30.0 * x.numel())
+        timer_end(t0, "style_dec_blur_bwd_kernel" if blur else "style_dec_bwd_kernel", 30.0 * x.numel())
+    if blur and want_dx and not style_dec_blur_bwd_fused(H, W):
+        dx = style_blur(dx)  # (a plane beyond the LDS bound: the kernel left the gradient with respect to blur(x))
     return dx, dnw, dbias, dstyle
 
 
-def style_enc_fwd(x, bias, eps=1e-5):
-    """-> (xn, mean [B, C], std [B, C]) of t = lrelu_0.2(x + bias): xn = (t - mean) / sqrt(var + eps), std = sqrt(var)"""
+def style_dec_blur_bwd_fused(H, W):
+    """does style_dec_bwd(..., blur=True) finish in one launch at this plane size (the plane staged in LDS)"""
+    return bool(_lib.load().sivae_style_dec_blur_bwd_fused(int(H), int(W)))
+
+
+def style_enc_fwd(x, bias, eps=1e-5, blur=False):
+    """-> (xn, mean [B, C], std [B, C]) of t = lrelu_0.2(x + bias): xn = (t - mean) / sqrt(var + eps), std = sqrt(var).
+    blur=True: style_blur(xn) in the place of xn, bit for bit (xn itself is not written)"""
     _style_f32("style_enc_fwd", x, bias)
     B, C, H, W = _style_dims("style_enc_fwd", x, bias)
     xn = torch.empty_like(x)
     mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
     std = torch.empty((B, C), dtype=torch.float32, device=x.device)
     t0 = timer_begin()
-    _lib.call("sivae_style_enc_fwd", _p(x), _p(bias), _p(xn), _p(mean), _p(std), B, C, H, W, float(eps), _s(x))
+    _lib.call("sivae_style_enc_blur_fwd" if blur else "sivae_style_enc_fwd", _p(x), _p(bias), _p(xn), _p(mean), _p(std),
+              B, C, H, W, float(eps), _s(x))
     if t0 is not None:
-        timer_end(t0, "style_enc_fwd_kernel", 8.0 * x.numel())
+        timer_end(t0, "style_enc_blur_fwd_kernel" if blur else "style_enc_fwd_kernel", 8.0 * x.numel())
     return xn, mean, std
 
 
-def style_enc_bwd(dxn, dmean, dstd, x, bias, mean, std, eps=1e-5, want_dx=True, want_dbias=True):
+def style_enc_bwd(dxn, dmean, dstd, x, bias, mean, std, eps=1e-5, want_dx=True, want_dbias=True, blur=False):
     """-> (dx, dbias [C]) from the three upstream gradients (each may be None: zero); where std == 0 the dstd term is
-    dropped (the reference's gradient is NaN there)"""
+    dropped (the reference's gradient is NaN there).  blur=True: dxn is the gradient of style_blur(xn); the kernel reads
+    its blur by 9 taps"""
     _style_f32("style_enc_bwd", dxn, dmean, dstd, x, bias, mean, std)
     B, C, H, W = _style_dims("style_enc_bwd", x, bias)
     if (dxn is not None and dxn.shape != x.shape) or any(t is not None and tuple(t.shape) != (B, C)
@@ -1680,12 +1695,14 @@ def style_enc_bwd(dxn, dmean, dstd, x, bias, mean, std, eps=1e-5, want_dx=True, 
         raise ValueError("sivae_hip.style_enc_bwd: dxn like x and dmean, dstd, mean, std [B, C] expected")
     dx = torch.empty_like(x) if want_dx else None
     dbias = torch.empty(C, dtype=torch.float32, device=x.device) if want_dbias else None
-    ws = workspace(_lib.load().sivae_style_enc_bwd_workspace_bytes(B, C), x.device) if want_dbias else None
+    L = _lib.load()
+    ws_bytes = (L.sivae_style_enc_blur_bwd_workspace_bytes if blur else L.sivae_style_enc_bwd_workspace_bytes)(B, C)
+    ws = workspace(ws_bytes, x.device) if want_dbias else None
     t0 = timer_begin()
-    _lib.call("sivae_style_enc_bwd", _p(dxn), _p(dmean), _p(dstd), _p(x), _p(bias), _p(mean), _p(std), _p(dx), _p(dbias),
-              B, C, H, W, float(eps), _p(ws), 0 if ws is None else ws.numel(), _s(x))
+    _lib.call("sivae_style_enc_blur_bwd" if blur else "sivae_style_enc_bwd", _p(dxn), _p(dmean), _p(dstd), _p(x), _p(bias),
+              _p(mean), _p(std), _p(dx), _p(dbias), B, C, H, W, float(eps), _p(ws), 0 if ws is None else ws.numel(), _s(x))
     if t0 is not None:
-        timer_end(t0, "style_enc_bwd_kernel", 20.0 * x.numel())
+        timer_end(t0, "style_enc_blur_bwd_kernel" if blur else "style_enc_bwd_kernel", 20.0 * x.numel())
     return dx, dbias
 
 

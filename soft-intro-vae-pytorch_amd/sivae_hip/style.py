@@ -11,6 +11,10 @@ csrc/style.hip:
       m, std [B, C] -> InstanceNorm.  All three outputs are differentiable.  Where std == 0 (a constant plane) the
       reference's gradient is NaN; the kernel drops the dstd term there.
   blur(x) -> the depthwise [1, 2, 1] x [1, 2, 1] / 16 filter (net.py:49-60), its own adjoint.
+  style_layer(..., blur=True) is style_layer(blur(x), ...) and stat_norm(x, bias, blur=True) returns (blur(xn), m, std),
+      each still ONE kernel per direction and bit for bit the composition: the chain reads the 9 taps itself, the blurred
+      tensor is neither written nor saved (the decoder layer saves the unblurred x).  Above the LDS bound of the decoder
+      backward (ops.style_dec_blur_bwd_fused) its dx is finished by one ops.style_blur call.
 
 and the RGB layers with the level-of-detail blend on the kernels of csrc/rgb.hip:
 
@@ -68,14 +72,14 @@ def noise_mode(mode):
 
 class StyleLayerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, noise_weight, bias, style, noise, mode, layer, eps):
+    def forward(ctx, x, noise_weight, bias, style, noise, mode, layer, eps, blur=False):
         x, style = x.contiguous(), style.contiguous()
         nw = None if mode == ops.STYLE_NOISE_NONE else noise_weight.detach().reshape(-1)
         nz = None if mode == ops.STYLE_NOISE_NONE else noise.contiguous()
         b_ = bias.detach().reshape(-1)
-        y, mean, rstd = ops.style_dec_fwd(x, nz, nw, b_, style, mode, layer, eps)
-        ctx.mode, ctx.layer = mode, layer
-        ctx.save_for_backward(x, noise_weight, bias, style, nz, mean, rstd)
+        y, mean, rstd = ops.style_dec_fwd(x, nz, nw, b_, style, mode, layer, eps, blur=blur)
+        ctx.mode, ctx.layer, ctx.blur = mode, layer, blur
+        ctx.save_for_backward(x, noise_weight, bias, style, nz, mean, rstd)  # (blur: the unblurred x)
         return y
 
     @staticmethod
@@ -87,18 +91,18 @@ class StyleLayerFn(torch.autograd.Function):
         nw = None if ctx.mode == ops.STYLE_NOISE_NONE else noise_weight.detach().reshape(-1)
         dx, dnw, db, ds = ops.style_dec_bwd(dy.contiguous(), x, nz, nw, bias.detach().reshape(-1), style, mean, rstd,
                                             ctx.mode, ctx.layer, want_dx=need[0], want_dnw=need[1], want_dbias=need[2],
-                                            want_dstyle=need[3])
+                                            want_dstyle=need[3], blur=ctx.blur)
         # (mode 0: noise_weight takes no part and gets no gradient, as in the reference)
         return (dx, None if dnw is None else dnw.view_as(noise_weight), None if db is None else db.view_as(bias), ds,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 class StatNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, bias, eps):
+    def forward(ctx, x, bias, eps, blur=False):
         x = x.contiguous()
-        xn, mean, std = ops.style_enc_fwd(x, bias.detach().reshape(-1), eps)
-        ctx.eps = eps
+        xn, mean, std = ops.style_enc_fwd(x, bias.detach().reshape(-1), eps, blur=blur)
+        ctx.eps, ctx.blur = eps, blur
         ctx.save_for_backward(x, bias, mean, std)
         return xn, mean, std
 
@@ -108,8 +112,8 @@ class StatNormFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         c = lambda t: None if t is None else t.contiguous()  # noqa: E731
         dx, db = ops.style_enc_bwd(c(dxn), c(dmean), c(dstd), x, bias.detach().reshape(-1), mean, std, ctx.eps,
-                                   want_dx=need[0], want_dbias=need[1])
-        return dx, None if db is None else db.view_as(bias), None
+                                   want_dx=need[0], want_dbias=need[1], blur=ctx.blur)
+        return dx, None if db is None else db.view_as(bias), None, None
 
 
 class BlurFn(torch.autograd.Function):
@@ -163,15 +167,15 @@ class FromRGBFn(torch.autograd.Function):
         return di, None if dw is None else dw.view_as(weight), db, None, do, None
 
 
-def style_layer(x, noise_weight, bias, style, noise=None, mode=None, layer=0, eps=1e-8):
+def style_layer(x, noise_weight, bias, style, noise=None, mode=None, layer=0, eps=1e-8, blur=False):
     mode = noise_mode(mode)
     if mode != ops.STYLE_NOISE_NONE and noise is None:
         raise ValueError("sivae_hip.style_layer: noise mode %d needs the noise tensor" % mode)
-    return StyleLayerFn.apply(x, noise_weight, bias, style, noise, mode, int(layer), float(eps))
+    return StyleLayerFn.apply(x, noise_weight, bias, style, noise, mode, int(layer), float(eps), bool(blur))
 
 
-def stat_norm(x, bias, eps=1e-5):
-    return StatNormFn.apply(x, bias, float(eps))
+def stat_norm(x, bias, eps=1e-5, blur=False):
+    return StatNormFn.apply(x, bias, float(eps), bool(blur))
 
 
 def blur(x):

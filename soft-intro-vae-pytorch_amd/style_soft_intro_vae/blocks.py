@@ -13,6 +13,9 @@ implicit learning-rate-equalised form (its default) is built.  What follows each
 (one fused kernel per chain and direction), the 3x3 stride-1 convolutions on sivae_hip.functional.conv_bias, the linears
 on functional.linear, the fused_scale=True convolutions (stride 2 with the transformed kernel, the resolutions from 128
 up) on functional.conv_upscale / conv_downscale: the phase-form upsample-convolution kernels run one way or the other.
+The blur in front of the decoder's first layer and behind the encoder's first norm is folded into that chain
+(style.style_layer / stat_norm with blur=True: no blur launch, no blurred tensor, the same bits); the Blur module and its
+buffer stay for the state dict.  SIVAE_STYLE_FUSE_BLUR=0 restores the separate calls.
 Still torch here: upscale2d and downscale2d around the fused_scale=False pairs.  ROCm device tensors only: there is no
 CPU path (the convolutions alone still take CPU tensors through torch's).
 """
@@ -30,6 +33,17 @@ from sivae_hip import ops, style
 # SIVAE_STYLE_SCALE_CONV=0: the fused_scale convolutions stay on torch's stride-2 convolutions (read at call time: tests
 # and tools assign blocks.SCALE_CONV)
 SCALE_CONV = os.environ.get("SIVAE_STYLE_SCALE_CONV", "1") != "0"
+# SIVAE_STYLE_FUSE_BLUR=0: the blur stays a call and an autograd node of its own in front of the decoder's first layer
+# and behind the encoder's first norm (read at call time, like SCALE_CONV)
+FUSE_BLUR = os.environ.get("SIVAE_STYLE_FUSE_BLUR", "1") != "0"
+# Decoder planes above this many elements keep the composition (None: no limit).  It is the LDS bound of csrc/style.hip's
+# decoder backward (ST_BLUR_LDS_MAX): above it the fused pair still ends with a blur launch, and that class, 256 x 256,
+# measured as a loss (README, profiles/style_blur_bench.txt).  The encoder's pair gained at every shape and has no limit.
+FUSE_BLUR_DEC_MAX_HW = 16384
+
+
+def _fuse_blur_dec(x):
+    return FUSE_BLUR and (FUSE_BLUR_DEC_MAX_HW is None or x.shape[2] * x.shape[3] <= FUSE_BLUR_DEC_MAX_HW)
 
 
 def pixel_norm(x, epsilon=1e-8):
@@ -136,12 +150,14 @@ class EncodeBlock(nn.Module):
         self.style_2 = _Linear(outputs if last else 2 * outputs, latent_size)
 
     def forward(self, x):
-        x, m, std = style.stat_norm(self.conv_1(x), self.bias_1)
+        x = self.conv_1(x)
+        fuse = FUSE_BLUR and not self.last
+        x, m, std = style.stat_norm(x, self.bias_1, blur=True) if fuse else style.stat_norm(x, self.bias_1)
         w1 = self.style_1(torch.cat((m, std), dim=1))
         if self.last:
             x = F.leaky_relu(self.dense(x.view(x.shape[0], -1)), 0.2)
             return x, w1, self.style_2(x)
-        x = self.conv_2(self.blur(x))
+        x = self.conv_2(x if fuse else self.blur(x))
         if not self.fused_scale:
             x = downscale2d(x)
         x, m, std = style.stat_norm(x, self.bias_2)
@@ -163,18 +179,24 @@ class DecodeBlock(nn.Module):
         self.bias_2 = nn.Parameter(torch.zeros(1, outputs, 1, 1))
         self.style_2 = _Linear(latent_size, 2 * outputs, gain=1)
 
-    def _layer(self, x, noise_weight, bias, s, noise):
+    def _layer(self, x, noise_weight, bias, s, noise, blur=False):
         mode = style.noise_mode(noise)
         nz = None
         if mode:  # (drawn here, shape and order as in the reference: one tensor per layer, the first layer's first)
             nz = torch.randn([1 if mode == ops.STYLE_NOISE_BATCH_CONSTANT else x.shape[0], 1, x.shape[2], x.shape[3]],
                              device=x.device)
+        if blur:  # (the layer reads blur(x) from x; without it the call stays the one it was)
+            return style.style_layer(x, noise_weight, bias, s, nz, mode, self.layer, blur=True)
         return style.style_layer(x, noise_weight, bias, s, nz, mode, self.layer)
 
     def forward(self, x, s1, s2, noise):
+        fuse = False
         if self.has_first_conv:
             if not self.fused_scale:
                 x = upscale2d(x)
-            x = self.blur(self.conv_1(x))
-        x = self._layer(x, self.noise_weight_1, self.bias_1, self.style_1(s1), noise)
+            x = self.conv_1(x)
+            fuse = _fuse_blur_dec(x)
+            if not fuse:
+                x = self.blur(x)
+        x = self._layer(x, self.noise_weight_1, self.bias_1, self.style_1(s1), noise, fuse)
         return self._layer(self.conv_2(x), self.noise_weight_2, self.bias_2, self.style_2(s2), noise)
