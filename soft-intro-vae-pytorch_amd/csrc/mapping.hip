@@ -18,9 +18,8 @@
 //   styles:      one thread per (sample, quad), the layers walked in ascending l.
 // Plain grids, bounded loops, no atomics, no cooperative launch: every order is fixed by the shape alone, two runs are
 // bit-identical, and a sample's pixel-norm / styles result (without the running average) does not depend on the batch.
-#include <initializer_list>
-
 #include "common.h"
+#include "chunk4.h"
 
 // No contraction of a * b + c by the optimiser anywhere in this file (it may differ between the two instantiations of one
 // kernel); the multiply-adds that are wanted are written out as fmaf.
@@ -32,54 +31,19 @@
 
 namespace {
 
-// A plain float* would be a generic pointer and every access a flat_ one: cast to the GLOBAL address space.
-typedef __attribute__((address_space(1))) float map_gf32;
-typedef __attribute__((address_space(1))) const float map_gcf32;
-typedef __attribute__((address_space(1))) f32x4 map_gf32x4;
-typedef __attribute__((address_space(1))) const f32x4 map_gcf32x4;
-
-__device__ __forceinline__ map_gcf32* map_g(const float* p) { return (map_gcf32*)p; }
-__device__ __forceinline__ map_gf32* map_g(float* p) { return (map_gf32*)p; }
-
-// elements i .. i + 3 of a row of n: one 16-byte access (AL: n % 4 == 0, so all four exist) or guarded scalars
-template <bool AL>
-__device__ __forceinline__ void map_load4(map_gcf32* __restrict__ p, int i, int n, float (&v)[4]) {
-  if (AL) {
-    const f32x4 q = *reinterpret_cast<map_gcf32x4*>(p + i);
-    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? p[i + j] : 0.f;
-  }
-}
-template <bool AL>
-__device__ __forceinline__ void map_store4(map_gf32* __restrict__ p, int i, int n, const float (&v)[4]) {
-  if (AL) {
-    f32x4 q;
-    q[0] = v[0], q[1] = v[1], q[2] = v[2], q[3] = v[3];
-    *reinterpret_cast<map_gf32x4*>(p + i) = q;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = v[j];
-  }
-}
-
-// torch's lerp (ATen/native/Lerp.h)
-__device__ __forceinline__ float map_lerp(float a, float b, float w) {
-  const float d = b - a;
-  return fabsf(w) < 0.5f ? a + w * d : b - d * (1.f - w);
-}
+// every row goes through the GLOBAL address space (chunk4.h); its quads are read and written with c4_load / c4_store
+__device__ __forceinline__ c4_gcf32* map_g(const float* p) { return (c4_gcf32*)p; }
+__device__ __forceinline__ c4_gf32* map_g(float* p) { return (c4_gf32*)p; }
 
 // ---- pixel-norm ---------------------------------------------------------------------------------------------------------
 // sum_z a[z] b[z] of one row by one wave: the lane's quads in ascending order, j ascending inside a quad, then the lanes
 template <bool AL>
-__device__ __forceinline__ double map_row_dot(map_gcf32* __restrict__ a, map_gcf32* __restrict__ b, int Z, int lane) {
+__device__ __forceinline__ double map_row_dot(c4_gcf32* __restrict__ a, c4_gcf32* __restrict__ b, int Z, int lane) {
   float acc = 0.f;
   for (int i = lane * 4; i < Z; i += 256) {
     float u[4], v[4];
-    map_load4<AL>(a, i, Z, u);
-    map_load4<AL>(b, i, Z, v);
+    c4_load<AL>(a, i, Z, u);
+    c4_load<AL>(b, i, Z, v);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc = fmaf(u[j], v[j], acc);
   }
@@ -92,17 +56,17 @@ __global__ void __launch_bounds__(MAP_NT) pixel_norm_fwd_kernel(const float* __r
                                                                 float* __restrict__ rfac, int B, int Z, float eps) {
   const int lane = threadIdx.x & 63, b = blockIdx.x * (MAP_NT / 64) + (threadIdx.x >> 6);
   if (b >= B) return;  // (whole waves leave: the butterfly below runs with every lane of its wave active)
-  map_gcf32* xr = map_g(x) + (size_t)b * Z;
-  map_gf32* yr = map_g(y) + (size_t)b * Z;
+  c4_gcf32* xr = map_g(x) + (size_t)b * Z;
+  c4_gf32* yr = map_g(y) + (size_t)b * Z;
   const double ss = map_row_dot<AL>(xr, xr, Z, lane);
   const float r = (float)(1.0 / sqrt(ss / (double)Z + (double)eps));
   if (lane == 0) map_g(rfac)[b] = r;
   for (int i = lane * 4; i < Z; i += 256) {
     float v[4];
-    map_load4<AL>(xr, i, Z, v);
+    c4_load<AL>(xr, i, Z, v);
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = v[j] * r;
-    map_store4<AL>(yr, i, Z, v);
+    c4_store<AL>(yr, i, Z, v);
   }
 }
 
@@ -113,20 +77,20 @@ __global__ void __launch_bounds__(MAP_NT) pixel_norm_bwd_kernel(const float* __r
                                                                 int Z) {
   const int lane = threadIdx.x & 63, b = blockIdx.x * (MAP_NT / 64) + (threadIdx.x >> 6);
   if (b >= B) return;
-  map_gcf32* xr = map_g(x) + (size_t)b * Z;
-  map_gcf32* gr = map_g(dy) + (size_t)b * Z;
-  map_gf32* dr = map_g(dx) + (size_t)b * Z;
+  c4_gcf32* xr = map_g(x) + (size_t)b * Z;
+  c4_gcf32* gr = map_g(dy) + (size_t)b * Z;
+  c4_gf32* dr = map_g(dx) + (size_t)b * Z;
   const double dot = map_row_dot<AL>(gr, xr, Z, lane);
   const float r = map_g(rfac)[b];
   const double r3 = (double)r * (double)r * (double)r;
   const float c = (float)(r3 * (dot / (double)Z));
   for (int i = lane * 4; i < Z; i += 256) {
     float g[4], v[4];
-    map_load4<AL>(gr, i, Z, g);
-    map_load4<AL>(xr, i, Z, v);
+    c4_load<AL>(gr, i, Z, g);
+    c4_load<AL>(xr, i, Z, v);
 #pragma unroll
     for (int j = 0; j < 4; ++j) g[j] = fmaf(-v[j], c, r * g[j]);
-    map_store4<AL>(dr, i, Z, g);
+    c4_store<AL>(dr, i, Z, g);
   }
 }
 
@@ -162,14 +126,14 @@ __global__ void __launch_bounds__(MAP_NT) lrelu_bias_bwd_kernel(const float* __r
     for (int b = b0; b < b1; ++b) {
       const size_t row = (size_t)b * N;
       float g[4];
-      map_load4<AL>(map_g(dy) + row, n, N, g);
+      c4_load<AL>(map_g(dy) + row, n, N, g);
       if (y) {
         float v[4];
-        map_load4<AL>(map_g(y) + row, n, N, v);
+        c4_load<AL>(map_g(y) + row, n, N, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j) g[j] = v[j] > 0.f ? g[j] : g[j] * slope;
       }
-      if (dz) map_store4<AL>(map_g(dz) + row, n, N, g);
+      if (dz) c4_store<AL>(map_g(dz) + row, n, N, g);
 #pragma unroll
       for (int j = 0; j < 4; ++j) s[j] += (double)g[j];
     }
@@ -194,7 +158,7 @@ __global__ void __launch_bounds__(MAP_NT) styles_avg_kernel(const float* __restr
   if (z < Z) {
     for (int b = b0; b < b1; ++b) {
       float v[4];
-      map_load4<AL>(map_g(s) + (size_t)b * Z, z, Z, v);
+      c4_load<AL>(map_g(s) + (size_t)b * Z, z, Z, v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) t[j] += (double)v[j];
     }
@@ -205,10 +169,10 @@ __global__ void __launch_bounds__(MAP_NT) styles_avg_kernel(const float* __restr
   for (int j = 0; j < 4; ++j) m[j] = (float)(t[j] / (double)B);
   for (int l = 0; l < L; ++l) {
     float a[4];
-    map_load4<AL>(map_g((const float*)avg) + (size_t)l * Z, z, Z, a);
+    c4_load<AL>(map_g((const float*)avg) + (size_t)l * Z, z, Z, a);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] = map_lerp(a[j], m[j], w);
-    map_store4<AL>(map_g(avg) + (size_t)l * Z, z, Z, a);
+    for (int j = 0; j < 4; ++j) a[j] = c4_lerp(a[j], m[j], w, 1.f - w);
+    c4_store<AL>(map_g(avg) + (size_t)l * Z, z, Z, a);
   }
 }
 
@@ -229,20 +193,20 @@ __global__ void __launch_bounds__(MAP_NT) styles_fwd_kernel(StylesArgs a) {
   if (e >= (size_t)a.B * a.qpr) return;
   const int b = (int)(e / a.qpr), z = (int)(e - (size_t)b * a.qpr) * 4, Z = a.Z;
   float v1[4], v2[4] = {0.f, 0.f, 0.f, 0.f};
-  map_load4<AL>(map_g(a.s) + (size_t)b * Z, z, Z, v1);
-  if (a.mix_cutoff < a.L) map_load4<AL>(map_g(a.s2) + (size_t)b * Z, z, Z, v2);
-  map_gf32* out = map_g(a.styles) + (size_t)b * a.L * Z;
+  c4_load<AL>(map_g(a.s) + (size_t)b * Z, z, Z, v1);
+  if (a.mix_cutoff < a.L) c4_load<AL>(map_g(a.s2) + (size_t)b * Z, z, Z, v2);
+  c4_gf32* out = map_g(a.styles) + (size_t)b * a.L * Z;
   for (int l = 0; l < a.L; ++l) {
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = l < a.mix_cutoff ? v1[j] : v2[j];
     if (l < a.trunc_cutoff) {
       float m[4];
-      map_load4<AL>(map_g(a.avg) + (size_t)l * Z, z, Z, m);
+      c4_load<AL>(map_g(a.avg) + (size_t)l * Z, z, Z, m);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = map_lerp(m[j], o[j], a.psi);
+      for (int j = 0; j < 4; ++j) o[j] = c4_lerp(m[j], o[j], a.psi, 1.f - a.psi);
     }
-    map_store4<AL>(out + (size_t)l * Z, z, Z, o);
+    c4_store<AL>(out + (size_t)l * Z, z, Z, o);
   }
 }
 
@@ -253,11 +217,11 @@ __global__ void __launch_bounds__(MAP_NT) styles_bwd_kernel(StylesArgs a) {
   const size_t e = (size_t)blockIdx.x * MAP_NT + threadIdx.x;
   if (e >= (size_t)a.B * a.qpr) return;
   const int b = (int)(e / a.qpr), z = (int)(e - (size_t)b * a.qpr) * 4, Z = a.Z;
-  map_gcf32* g = map_g(a.dstyles) + (size_t)b * a.L * Z;
+  c4_gcf32* g = map_g(a.dstyles) + (size_t)b * a.L * Z;
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   for (int l = 0; l < a.L; ++l) {
     float v[4];
-    map_load4<AL>(g + (size_t)l * Z, z, Z, v);
+    c4_load<AL>(g + (size_t)l * Z, z, Z, v);
     const float c = l < a.trunc_cutoff ? a.psi : 1.f;
     if (l < a.mix_cutoff) {
 #pragma unroll
@@ -267,22 +231,11 @@ __global__ void __launch_bounds__(MAP_NT) styles_bwd_kernel(StylesArgs a) {
       for (int j = 0; j < 4; ++j) s2[j] = fmaf(c, v[j], s2[j]);
     }
   }
-  if (a.ds) map_store4<AL>(map_g(a.ds) + (size_t)b * Z, z, Z, s1);
-  if (a.ds2) map_store4<AL>(map_g(a.ds2) + (size_t)b * Z, z, Z, s2);
+  if (a.ds) c4_store<AL>(map_g(a.ds) + (size_t)b * Z, z, Z, s1);
+  if (a.ds2) c4_store<AL>(map_g(a.ds2) + (size_t)b * Z, z, Z, s2);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-bool map_al4(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (p && sivae_misaligned(p, 4)) return false;
-  return true;
-}
-bool map_al16(int row, std::initializer_list<const void*> ptrs) {
-  if (row % 4) return false;
-  for (const void* p : ptrs)
-    if (p && sivae_misaligned(p, 16)) return false;
-  return true;
-}
 // rows x row length: a tensor of the call stays below 2^31 elements (the quad and block counts are 32-bit)
 int map_check(long long rows, long long cols) {
   if (rows <= 0 || cols <= 0) return SIVAE_ERR_SHAPE;
@@ -302,8 +255,8 @@ extern "C" int sivae_pixel_norm_fwd(const float* x, float* y, float* rfac, int B
   if (!x || !y || !rfac) return SIVAE_ERR_NULL;
   const int rc = map_check(B, Z);
   if (rc != SIVAE_OK) return rc;
-  if (!(eps >= 0.f) || !map_al4({x, y, rfac})) return SIVAE_ERR_SHAPE;
-  const bool al = map_al16(Z, {x, y});
+  if (!(eps >= 0.f) || !c4_al4({x, y, rfac})) return SIVAE_ERR_SHAPE;
+  const bool al = c4_al16(Z, {x, y});
   MAP_LAUNCH(pixel_norm_fwd_kernel, al, dim3((unsigned)cdiv(B, MAP_NT / 64)), stream, x, y, rfac, B, Z, eps);
   return sivae_launch_status();
 }
@@ -313,8 +266,8 @@ extern "C" int sivae_pixel_norm_bwd(const float* dy, const float* x, const float
   if (!dy || !x || !rfac || !dx) return SIVAE_ERR_NULL;
   const int rc = map_check(B, Z);
   if (rc != SIVAE_OK) return rc;
-  if (!map_al4({dy, x, rfac, dx})) return SIVAE_ERR_SHAPE;
-  const bool al = map_al16(Z, {dy, x, dx});
+  if (!c4_al4({dy, x, rfac, dx})) return SIVAE_ERR_SHAPE;
+  const bool al = c4_al16(Z, {dy, x, dx});
   MAP_LAUNCH(pixel_norm_bwd_kernel, al, dim3((unsigned)cdiv(B, MAP_NT / 64)), stream, dy, x, rfac, dx, B, Z);
   return sivae_launch_status();
 }
@@ -325,9 +278,9 @@ extern "C" int sivae_lrelu_bias_bwd(const float* dy, const float* y, float slope
   const int rc = map_check(B, N);
   if (rc != SIVAE_OK) return rc;
   if (!(slope >= 0.f && slope <= 1.f)) return SIVAE_ERR_MODE;
-  if (!map_al4({dy, y, dz, dbias})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({dy, y, dz, dbias})) return SIVAE_ERR_SHAPE;
   if (!dz && !dbias) return SIVAE_OK;
-  const bool al = map_al16(N, {dy, y, dz});
+  const bool al = c4_al16(N, {dy, y, dz});
   MAP_LAUNCH(lrelu_bias_bwd_kernel, al, dim3((unsigned)cdiv(N, 4 * MAP_CQ)), stream, dy, y, slope, dz, dbias, B, N);
   return sivae_launch_status();
 }
@@ -351,8 +304,8 @@ extern "C" int sivae_styles_fwd(const float* s, const float* s2, int mix_cutoff,
   if (rc != SIVAE_OK) return rc;
   if ((update_avg || truncate) && !avg) return SIVAE_ERR_NULL;
   if (update_avg && !(avg_weight >= 0.f && avg_weight <= 1.f)) return SIVAE_ERR_MODE;
-  if (!map_al4({s, s2, avg, styles})) return SIVAE_ERR_SHAPE;
-  const bool al = map_al16(Z, {s, s2, avg, styles});
+  if (!c4_al4({s, s2, avg, styles})) return SIVAE_ERR_SHAPE;
+  const bool al = c4_al16(Z, {s, s2, avg, styles});
   if (update_avg) {
     MAP_LAUNCH(styles_avg_kernel, al, dim3((unsigned)cdiv(Z, 4 * MAP_CQ)), stream, s, avg, avg_weight, B, L, Z);
     const int st = sivae_launch_status();
@@ -375,9 +328,9 @@ extern "C" int sivae_styles_bwd(const float* dstyles, int has_s2, int mix_cutoff
   const int rc = styles_check(has_s2, mix_cutoff, truncate, trunc_cutoff, B, L, Z);
   if (rc != SIVAE_OK) return rc;
   if (ds2 && !has_s2) return SIVAE_ERR_MODE;
-  if (!map_al4({dstyles, ds, ds2})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({dstyles, ds, ds2})) return SIVAE_ERR_SHAPE;
   if (!ds && !ds2) return SIVAE_OK;
-  const bool al = map_al16(Z, {dstyles, ds, ds2});
+  const bool al = c4_al16(Z, {dstyles, ds, ds2});
   StylesArgs a = {};
   a.dstyles = dstyles, a.ds = ds, a.ds2 = ds2;
   a.B = B, a.L = L, a.Z = Z, a.qpr = cdiv(Z, 4);

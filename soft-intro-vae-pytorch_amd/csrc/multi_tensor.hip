@@ -31,6 +31,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "chunk4.h"
 
 // No contraction of a * b + c across this file (as in style.hip): hipcc's default fuses as the optimiser sees fit, and
 // the reference's sequence of torch ops rounds after every operation.
@@ -69,49 +70,22 @@ __device__ __forceinline__ int mt_find(const MtTable<NP>& tab, int b) {
   return lo;
 }
 
-// The table's addresses are integers: cast to the GLOBAL address space they become global_load / global_store, a plain
-// float* would be a generic pointer and every access a flat_ one.
-typedef __attribute__((address_space(1))) float mt_gf32;
-typedef __attribute__((address_space(1))) const float mt_gcf32;
-typedef __attribute__((address_space(1))) f32x4 mt_gf32x4;
-typedef __attribute__((address_space(1))) const f32x4 mt_gcf32x4;
-
-// elements i .. i + 3 of a chunk with n elements left: one 16-byte access when AL and all four exist, else scalars
-template <bool AL>
-__device__ __forceinline__ void mt_load4(mt_gcf32* __restrict__ p, unsigned i, unsigned n, float (&v)[4]) {
-  if (AL && i + 4 <= n) {
-    const f32x4 q = *reinterpret_cast<mt_gcf32x4*>(p + i);
-    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? p[i + j] : 0.f;
-  }
-}
-template <bool AL>
-__device__ __forceinline__ void mt_store4(mt_gf32* __restrict__ p, unsigned i, unsigned n, const float (&v)[4]) {
-  if (AL && i + 4 <= n) {
-    f32x4 q;
-    q[0] = v[0], q[1] = v[1], q[2] = v[2], q[3] = v[3];
-    *reinterpret_cast<mt_gf32x4*>(p + i) = q;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = v[j];
-  }
-}
-
+// The table's addresses are integers: they are cast to the GLOBAL address space (chunk4.h).  Elements i .. i + 3 of a chunk
+// with n elements left are chunk4.h's c4_load / c4_store in their !FULL form: one 16-byte access when AL and all four
+// exist, else scalars (a tensor's alignment bit says nothing about its tail).
+//
 // reference: custom_adam.py:82-95
 template <bool AL>
-__device__ __forceinline__ void mt_adam_chunk(mt_gf32* __restrict__ p, mt_gcf32* __restrict__ g, mt_gf32* __restrict__ v,
+__device__ __forceinline__ void mt_adam_chunk(c4_gf32* __restrict__ p, c4_gcf32* __restrict__ g, c4_gf32* __restrict__ v,
                                               unsigned n, float s, float beta2, float omb, float eps) {
   float pv[MT_TRIPS][4], gv[MT_TRIPS][4], vv[MT_TRIPS][4];
 #pragma unroll
   for (int k = 0; k < MT_TRIPS; ++k) {  // (every load of the chunk is issued before the first result is needed)
     const unsigned i = (k * MT_NT + threadIdx.x) * 4;
     if (i < n) {
-      mt_load4<AL>(g, i, n, gv[k]);
-      mt_load4<AL>(v, i, n, vv[k]);
-      mt_load4<AL>(p, i, n, pv[k]);
+      c4_load<AL, false>(g, i, n, gv[k]);
+      c4_load<AL, false>(v, i, n, vv[k]);
+      c4_load<AL, false>(p, i, n, pv[k]);
     }
   }
 #pragma unroll
@@ -131,8 +105,8 @@ __device__ __forceinline__ void mt_adam_chunk(mt_gf32* __restrict__ p, mt_gcf32*
         vv[k][j] = vn;
         pv[k][j] = pv[k][j] - u;
       }
-      mt_store4<AL>(v, i, n, vv[k]);
-      mt_store4<AL>(p, i, n, pv[k]);
+      c4_store<AL, false>(v, i, n, vv[k]);
+      c4_store<AL, false>(p, i, n, pv[k]);
     }
   }
 }
@@ -141,9 +115,9 @@ __global__ void __launch_bounds__(MT_NT) mt_lreq_adam_kernel(MtTable<3> tab, flo
   const int b = blockIdx.x, t = mt_find(tab, b);
   const unsigned off = (unsigned)(b - tab.first[t]) * MT_C;  // (< MT_K * MT_C)
   const unsigned left = tab.n[t] - off, n = left < MT_C ? left : MT_C;
-  mt_gf32* p = reinterpret_cast<mt_gf32*>(tab.ptr[0][t]) + off;
-  mt_gcf32* g = reinterpret_cast<mt_gcf32*>(tab.ptr[1][t]) + off;
-  mt_gf32* v = reinterpret_cast<mt_gf32*>(tab.ptr[2][t]) + off;
+  c4_gf32* p = reinterpret_cast<c4_gf32*>(tab.ptr[0][t]) + off;
+  c4_gcf32* g = reinterpret_cast<c4_gcf32*>(tab.ptr[1][t]) + off;
+  c4_gf32* v = reinterpret_cast<c4_gf32*>(tab.ptr[2][t]) + off;
   const float s = tab.s[t];
   if ((tab.al[t >> 5] >> (t & 31)) & 1u)
     mt_adam_chunk<true>(p, g, v, n, s, beta2, omb, eps);
@@ -151,17 +125,18 @@ __global__ void __launch_bounds__(MT_NT) mt_lreq_adam_kernel(MtTable<3> tab, flo
     mt_adam_chunk<false>(p, g, v, n, s, beta2, omb, eps);
 }
 
-// reference: model.py:329 (torch's lerp_ with a scalar weight)
+// reference: model.py:329 (torch's lerp_ with a scalar weight).  The formula is chunk4.h's c4_lerp with the branch on |w|
+// taken once per block (`small`); calling c4_lerp per element gives the same values but another register allocation.
 template <bool AL>
-__device__ __forceinline__ void mt_lerp_chunk(mt_gf32* __restrict__ p, mt_gcf32* __restrict__ q, unsigned n, float w,
+__device__ __forceinline__ void mt_lerp_chunk(c4_gf32* __restrict__ p, c4_gcf32* __restrict__ q, unsigned n, float w,
                                               float omw, bool small) {
   float pv[MT_TRIPS][4], qv[MT_TRIPS][4];
 #pragma unroll
   for (int k = 0; k < MT_TRIPS; ++k) {
     const unsigned i = (k * MT_NT + threadIdx.x) * 4;
     if (i < n) {
-      mt_load4<AL>(q, i, n, qv[k]);
-      mt_load4<AL>(p, i, n, pv[k]);
+      c4_load<AL, false>(q, i, n, qv[k]);
+      c4_load<AL, false>(p, i, n, pv[k]);
     }
   }
 #pragma unroll
@@ -174,7 +149,7 @@ __device__ __forceinline__ void mt_lerp_chunk(mt_gf32* __restrict__ p, mt_gcf32*
         const float m = small ? w * d : d * omw;
         pv[k][j] = small ? pv[k][j] + m : qv[k][j] - m;
       }
-      mt_store4<AL>(p, i, n, pv[k]);
+      c4_store<AL, false>(p, i, n, pv[k]);
     }
   }
 }
@@ -183,8 +158,8 @@ __global__ void __launch_bounds__(MT_NT) mt_lerp_kernel(MtTable<2> tab, float w)
   const int b = blockIdx.x, t = mt_find(tab, b);
   const unsigned off = (unsigned)(b - tab.first[t]) * MT_C;
   const unsigned left = tab.n[t] - off, n = left < MT_C ? left : MT_C;
-  mt_gf32* p = reinterpret_cast<mt_gf32*>(tab.ptr[0][t]) + off;
-  mt_gcf32* q = reinterpret_cast<mt_gcf32*>(tab.ptr[1][t]) + off;
+  c4_gf32* p = reinterpret_cast<c4_gf32*>(tab.ptr[0][t]) + off;
+  c4_gcf32* q = reinterpret_cast<c4_gcf32*>(tab.ptr[1][t]) + off;
   const bool small = fabsf(w) < 0.5f;
   const float omw = 1.f - w;
   if ((tab.al[t >> 5] >> (t & 31)) & 1u)

@@ -17,9 +17,8 @@
 //                block order in fp64.
 // No atomics, every order is fixed by (C, H W) alone: two runs are bit-identical, a sample's forward result does not
 // depend on the batch, and the alignment changes no bit.  The weights are read with wave-uniform indices (scalar loads).
-#include <initializer_list>
-
 #include "common.h"
+#include "chunk4.h"
 
 // No contraction of a * b + c by the optimiser anywhere in this file (it differs between the two instantiations of one
 // kernel); the multiply-adds of the three bodies are written out as fmaf, which both instantiations execute alike.
@@ -34,32 +33,7 @@ __device__ __forceinline__ float rgb_lrelu2(float t) {
   const float u = t > 0.f ? t : t * 0.2f;
   return u > 0.f ? u : u * 0.2f;
 }
-// torch's lerp with a scalar weight (ATen/native/Lerp.h), 1 - w formed in fp32
-__device__ __forceinline__ float rgb_lerp(float a, float b, float w, float omw) {
-  const float d = b - a;
-  return fabsf(w) < 0.5f ? a + w * d : b - d * omw;
-}
-
-template <bool AL>
-__device__ __forceinline__ void rgb_load4(const float* __restrict__ p, int i, int n, float (&v)[4]) {
-  if (AL) {
-    const float4 q = *reinterpret_cast<const float4*>(p + i);
-    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? p[i + j] : 0.f;
-  }
-}
-template <bool AL>
-__device__ __forceinline__ void rgb_store4(float* __restrict__ p, int i, int n, const float (&v)[4]) {
-  if (AL) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = v[j];
-  }
-}
+// (a lane's 4 pixels are read and written with chunk4.h's c4_load / c4_store, the blends are its c4_lerp)
 
 // ---- the three bodies --------------------------------------------------------------------------------------------------
 // contraction: acc[k][j] += w[k ws] v[j], k ascending (w: wave-uniform)
@@ -134,7 +108,7 @@ __device__ __forceinline__ void rgb_load_img(const float* __restrict__ img, bool
   if (!pool) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      if (i < n) rgb_load4<AL>(img + (size_t)k * n, i, n, im[k]);
+      if (i < n) c4_load<AL>(img + (size_t)k * n, i, n, im[k]);
       else im[k][0] = im[k][1] = im[k][2] = im[k][3] = 0.f;
     }
     return;
@@ -179,7 +153,7 @@ __global__ void __launch_bounds__(RGB_NT) rgb_to_fwd_kernel(RgbArgs a) {
 #pragma unroll 4
     for (int c = c0; c < c1; ++c, xp += n) {
       float v[4];
-      rgb_load4<AL>(xp, i, n, v);
+      c4_load<AL>(xp, i, n, v);
       rgb_contract<K>(acc, a.w + c, C, v);
     }
   }
@@ -195,10 +169,10 @@ __global__ void __launch_bounds__(RGB_NT) rgb_to_fwd_kernel(RgbArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int p = i + j, h = p / W, w = p - h * W;
-      if (p < n) o[j] = rgb_lerp(pv[(h / 2) * W2 + w / 2], o[j], a.blend, a.omb);
+      if (p < n) o[j] = c4_lerp(pv[(h / 2) * W2 + w / 2], o[j], a.blend, a.omb);
     }
   }
-  rgb_store4<AL>(a.y + ((size_t)b * K + k) * n, i, n, o);
+  c4_store<AL>(a.y + ((size_t)b * K + k) * n, i, n, o);
 }
 
 // ---- from_rgb forward: the expansion, prologue the 2 x 2 average, epilogue lrelu2 and the blend with other ----------------
@@ -221,12 +195,12 @@ __global__ void __launch_bounds__(RGB_NT) rgb_from_fwd_kernel(RgbArgs a) {
     for (int j = 0; j < 4; ++j) t[j] = rgb_lrelu2(t[j]);
     if (op) {
       float ov[4];
-      rgb_load4<AL>(op, i, n, ov);
+      c4_load<AL>(op, i, n, ov);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) t[j] = rgb_lerp(t[j], ov[j], a.blend, a.omb);
+      for (int j = 0; j < 4; ++j) t[j] = c4_lerp(t[j], ov[j], a.blend, a.omb);
       op += n;
     }
-    rgb_store4<AL>(yp, i, n, t);
+    c4_store<AL>(yp, i, n, t);
   }
 }
 
@@ -243,7 +217,7 @@ __global__ void __launch_bounds__(RGB_NT) rgb_to_bwd_kernel(RgbArgs a) {
   float g[K][4];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    if (live) rgb_load4<AL>(a.dy + ((size_t)b * K + k) * n, i, n, g[k]);
+    if (live) c4_load<AL>(a.dy + ((size_t)b * K + k) * n, i, n, g[k]);
     else g[k][0] = g[k][1] = g[k][2] = g[k][3] = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) g[k][j] *= cg;
@@ -266,11 +240,11 @@ __global__ void __launch_bounds__(RGB_NT) rgb_to_bwd_kernel(RgbArgs a) {
       if (a.dx && live) {
         float o[4];
         rgb_expand<K>(o, 0.f, a.w + cc, C, g);
-        rgb_store4<AL>(a.dx + off, i, n, o);
+        c4_store<AL>(a.dx + off, i, n, o);
       }
       if (dw) {
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (live) rgb_load4<AL>(a.x + off, i, n, v);
+        if (live) c4_load<AL>(a.x + off, i, n, v);
         rgb_pair<K>(vals + 4 * u, g, v);
       }
     }
@@ -316,12 +290,12 @@ __global__ void __launch_bounds__(RGB_NT) rgb_from_bwd_kernel(RgbArgs a) {
       if (cc >= c1) break;
       const size_t off = base + (size_t)(cc - c0) * n;
       float dyv[4] = {0.f, 0.f, 0.f, 0.f}, da[4];
-      if (live) rgb_load4<AL>(a.dy + off, i, n, dyv);
+      if (live) c4_load<AL>(a.dy + off, i, n, dyv);
       if (a.daux && live) {
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = dyv[j] * a.blend;
-        rgb_store4<AL>(a.daux + off, i, n, o);
+        c4_store<AL>(a.daux + off, i, n, o);
       }
       if (!need_da) continue;
       float t[4];
@@ -341,7 +315,7 @@ __global__ void __launch_bounds__(RGB_NT) rgb_from_bwd_kernel(RgbArgs a) {
   if (!rgb_fold_waves<K>(red, acc, wv, lane, o) || !live) return;
   const int k = wv;
   if (!a.pool) {
-    rgb_store4<AL>(a.dx + ((size_t)b * K + k) * n, i, n, o);
+    c4_store<AL>(a.dx + ((size_t)b * K + k) * n, i, n, o);
     return;
   }
   float* q0 = a.dx + ((size_t)b * K + k) * 4 * n;
@@ -394,17 +368,6 @@ static int rgb_check(int B, int C, int H, int W, int K) {
   if (B > 65535 || (long long)H * W > 0x3fffffffLL || C > 0x3fffffff) return SIVAE_ERR_RANGE;
   return SIVAE_OK;
 }
-static bool rgb_al4(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (p && sivae_misaligned(p, 4)) return false;
-  return true;
-}
-static bool rgb_al16(int HW, std::initializer_list<const void*> ptrs) {
-  if (HW % 4) return false;
-  for (const void* p : ptrs)
-    if (p && sivae_misaligned(p, 16)) return false;
-  return true;
-}
 static size_t rgb_blocks(int B, int HW) { return (size_t)B * (size_t)cdiv(HW, RGB_TILE); }
 
 #define RGB_LAUNCH_K(KERN, K, al, grid, stream, args)                                   \
@@ -428,12 +391,12 @@ extern "C" int sivae_to_rgb_fwd(const float* x, const float* w, const float* bia
   const int rc = rgb_check(B, C, H, W, K);
   if (rc != SIVAE_OK) return rc;
   if (prev && ((H | W) & 1)) return SIVAE_ERR_SHAPE;
-  if (!rgb_al4({x, w, bias, prev, y})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({x, w, bias, prev, y})) return SIVAE_ERR_SHAPE;
   const int HW = H * W;
   RgbArgs a = {};
   a.x = x, a.w = w, a.bias = bias, a.aux = prev, a.y = y;
   a.C = C, a.HW = HW, a.W = W, a.cpw = cdiv(C, RGB_NW), a.blend = blend, a.omb = 1.f - blend;
-  const bool al = rgb_al16(HW, {x, y});
+  const bool al = c4_al16(HW, {x, y});
   const dim3 grid((unsigned)cdiv(HW, RGB_TILE), (unsigned)B);
   RGB_LAUNCH(rgb_to_fwd_kernel, K, al, grid, stream, a);
   return sivae_launch_status();
@@ -453,7 +416,7 @@ extern "C" int sivae_to_rgb_bwd(const float* dy, const float* x, const float* w,
   if (has_prev != 0 && has_prev != 1) return SIVAE_ERR_MODE;
   if (dprev && !has_prev) return SIVAE_ERR_MODE;
   if (has_prev && ((H | W) & 1)) return SIVAE_ERR_SHAPE;
-  if (!rgb_al4({dy, x, w, dx, dw, dbias, dprev})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({dy, x, w, dx, dw, dbias, dprev})) return SIVAE_ERR_SHAPE;
   const bool sums = dw || dbias;
   if (sums && (!workspace || sivae_misaligned(workspace, 16) || workspace_bytes < sivae_to_rgb_bwd_workspace_bytes(B, C, H, W, K)))
     return SIVAE_ERR_WORKSPACE;
@@ -465,7 +428,7 @@ extern "C" int sivae_to_rgb_bwd(const float* dy, const float* x, const float* w,
     a.blended = has_prev;
     a.C = C, a.HW = HW, a.W = W, a.cpw = cdiv(C, RGB_NW), a.sums = (dw ? 1 : 0) | (dbias ? 2 : 0);
     a.blend = blend, a.omb = 1.f - blend;
-    const bool al = rgb_al16(HW, {dy, dw ? x : nullptr, dx});
+    const bool al = c4_al16(HW, {dy, dw ? x : nullptr, dx});
     const dim3 grid((unsigned)cdiv(HW, RGB_TILE), (unsigned)B);
     RGB_LAUNCH(rgb_to_bwd_kernel, K, al, grid, stream, a);
     if (sums) {
@@ -490,12 +453,12 @@ extern "C" int sivae_from_rgb_fwd(const float* img, const float* w, const float*
   if (rc != SIVAE_OK) return rc;
   if (pool != 0 && pool != 1) return SIVAE_ERR_MODE;
   if (pool && ((H | W) & 1)) return SIVAE_ERR_SHAPE;
-  if (!rgb_al4({img, w, bias, other, y})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({img, w, bias, other, y})) return SIVAE_ERR_SHAPE;
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W, HW = Ho * Wo;
   RgbArgs a = {};
   a.x = img, a.w = w, a.bias = bias, a.aux = other, a.y = y;
   a.C = C, a.HW = HW, a.W = Wo, a.cpw = cdiv(C, RGB_NW), a.pool = pool, a.blend = blend, a.omb = 1.f - blend;
-  const bool al = rgb_al16(HW, {pool ? nullptr : img, other, y});
+  const bool al = c4_al16(HW, {pool ? nullptr : img, other, y});
   const dim3 grid((unsigned)cdiv(HW, RGB_TILE), (unsigned)B);
   RGB_LAUNCH(rgb_from_fwd_kernel, K, al, grid, stream, a);
   return sivae_launch_status();
@@ -516,7 +479,7 @@ extern "C" int sivae_from_rgb_bwd(const float* dy, const float* img, const float
   if ((pool != 0 && pool != 1) || (has_other != 0 && has_other != 1)) return SIVAE_ERR_MODE;
   if (dother && !has_other) return SIVAE_ERR_MODE;
   if (pool && ((H | W) & 1)) return SIVAE_ERR_SHAPE;
-  if (!rgb_al4({dy, img, w, bias, dimg, dw, dbias, dother})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({dy, img, w, bias, dimg, dw, dbias, dother})) return SIVAE_ERR_SHAPE;
   const bool sums = dw || dbias;
   if (sums && (!workspace || sivae_misaligned(workspace, 16) ||
                workspace_bytes < sivae_from_rgb_bwd_workspace_bytes(B, C, H, W, K, pool)))
@@ -528,7 +491,7 @@ extern "C" int sivae_from_rgb_bwd(const float* dy, const float* img, const float
   a.blended = has_other;
   a.part = sums ? static_cast<float*>(workspace) : nullptr;
   a.C = C, a.HW = HW, a.W = Wo, a.cpw = cdiv(C, RGB_NW), a.pool = pool, a.blend = blend, a.omb = 1.f - blend;
-  const bool al = rgb_al16(HW, {dy, pool ? nullptr : img, pool ? nullptr : dimg, dother});
+  const bool al = c4_al16(HW, {dy, pool ? nullptr : img, pool ? nullptr : dimg, dother});
   const dim3 grid((unsigned)cdiv(HW, RGB_TILE), (unsigned)B);
   RGB_LAUNCH(rgb_from_bwd_kernel, K, al, grid, stream, a);
   if (sums) {

@@ -21,9 +21,9 @@
 // there, larger ones are written as they are and the caller runs the blur kernel over them.  The stencil is st_blur9 for all
 // of them and for style_blur_kernel, so a fused chain gives the bits of the two kernels it replaces.
 #include <cmath>
-#include <initializer_list>
 
 #include "common.h"
+#include "chunk4.h"
 
 // No contraction of a * b + c across this file: hipcc's default fuses them as the optimiser sees fit, which differs between
 // the instantiations of one kernel (measured: the last bit of dx between the 16-byte and the scalar instantiation), and
@@ -57,27 +57,7 @@ __device__ __forceinline__ float st_dec_t(float x, float nz, const StPre& p) {
   return st_lrelu(u + p.bias);
 }
 
-// the chunk of 4 elements at i of a plane of n: 16-byte access when AL (then n % 4 == 0 and i < n), else guarded scalars
-template <bool AL>
-__device__ __forceinline__ void st_load4(const float* __restrict__ p, int i, int n, float (&v)[4]) {
-  if (AL) {
-    const float4 q = *reinterpret_cast<const float4*>(p + i);
-    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? p[i + j] : 0.f;
-  }
-}
-template <bool AL>
-__device__ __forceinline__ void st_store4(float* __restrict__ p, int i, int n, const float (&v)[4]) {
-  if (AL) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = v[j];
-  }
-}
+// (the chunk of 4 elements at i of a plane of n is chunk4.h's c4_load / c4_store: 16-byte access when AL, else guarded scalars)
 
 // f(k, i) for every chunk of the thread: k the chunk's register slot (compile-time after unrolling, HELD only), i its
 // first element.  HELD: the EPT / 4 slots, those at or past n skipped; streamed: as many as the plane has.
@@ -155,7 +135,7 @@ __device__ __forceinline__ void st_blur4(F&& at, F4&& at4, int i, int n, int H, 
 // ... of a plane in memory (global or LDS)
 template <bool AL>
 __device__ __forceinline__ void st_blur4_of(const float* __restrict__ p, int i, int n, int H, int W, float (&v)[4]) {
-  st_blur4<AL>([&](int q) { return p[q]; }, [&](int q, float(&c)[4]) { st_load4<true>(p, q, n, c); }, i, n, H, W, v);
+  st_blur4<AL>([&](int q) { return p[q]; }, [&](int q, float(&c)[4]) { c4_load<true>(p, q, n, c); }, i, n, H, W, v);
 }
 
 struct StDecFwdArgs {
@@ -189,8 +169,8 @@ __device__ __forceinline__ void st_dec_fwd(const StDecFwdArgs& a) {
     if constexpr (BL)
       st_blur4_of<AL>(x, i, n, a.H, a.W, xv);
     else
-      st_load4<AL>(x, i, n, xv);
-    if (p.mode) st_load4<AL>(nz, i, n, zv);
+      c4_load<AL>(x, i, n, xv);
+    if (p.mode) c4_load<AL>(nz, i, n, zv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) tv[j] = st_dec_t(xv[j], zv[j], p);
   };
@@ -224,7 +204,7 @@ __device__ __forceinline__ void st_dec_fwd(const StDecFwdArgs& a) {
     if (!HELD) load_t(i, tv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) yv[j] = fmaf(((HELD ? t[4 * k + j] : tv[j]) - m) * r, scale, shift);
-    st_store4<AL>(y, i, n, yv);
+    c4_store<AL>(y, i, n, yv);
   });
   if (tid == 0) a.mean[plane] = m, a.rstd[plane] = r;
 }
@@ -268,7 +248,7 @@ __device__ __forceinline__ void st_dec_bwd(const StDecBwdArgs& a) {
     if constexpr (BL)
       st_blur4_of<AL>(x, i, n, a.H, a.W, xv);
     else
-      st_load4<AL>(x, i, n, xv);
+      c4_load<AL>(x, i, n, xv);
   };
 
   // sum dy and sum dy xh (a chunk's elements past n load as zero gradients)
@@ -276,8 +256,8 @@ __device__ __forceinline__ void st_dec_bwd(const StDecBwdArgs& a) {
   st_chunks<NT, EPT>(n, tid, [&](int k, int i) {
     float xv[4], gv[4], zv[4] = {0.f, 0.f, 0.f, 0.f};
     load_x(i, xv);
-    st_load4<AL>(dy, i, n, gv);
-    if (p.mode) st_load4<AL>(nz, i, n, zv);
+    c4_load<AL>(dy, i, n, gv);
+    if (p.mode) c4_load<AL>(nz, i, n, zv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (HELD) xs[4 * k + j] = xv[j], gs[4 * k + j] = gv[j];
@@ -303,9 +283,9 @@ __device__ __forceinline__ void st_dec_bwd(const StDecBwdArgs& a) {
     float xv[4], gv[4], zv[4] = {0.f, 0.f, 0.f, 0.f}, ov[4];
     if (!HELD) {
       load_x(i, xv);
-      st_load4<AL>(dy, i, n, gv);
+      c4_load<AL>(dy, i, n, gv);
     }
-    if (p.mode) st_load4<AL>(nz, i, n, zv);  // (one plane per sample at the most: re-read from cache, not held)
+    if (p.mode) c4_load<AL>(nz, i, n, zv);  // (one plane per sample at the most: re-read from cache, not held)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float xe = HELD ? xs[4 * k + j] : xv[j], ge = HELD ? gs[4 * k + j] : gv[j];
@@ -318,16 +298,16 @@ __device__ __forceinline__ void st_dec_bwd(const StDecBwdArgs& a) {
       ov[j] = p.mode ? dp : dp * (1.f + p.c3 * xe * expf(p.c2 * xe * xe));
     }
     if (staged)
-      st_store4<AL>(stage, i, n, ov);
+      c4_store<AL>(stage, i, n, ov);
     else if (dx)
-      st_store4<AL>(dx, i, n, ov);
+      c4_store<AL>(dx, i, n, ov);
   });
   if (staged) {
     __syncthreads();
     st_chunks<NT, EPT>(n, tid, [&](int, int i) {
       float ov[4];
       st_blur4_of<AL>(stage, i, n, a.H, a.W, ov);
-      st_store4<AL>(dx, i, n, ov);
+      c4_store<AL>(dx, i, n, ov);
     });
   }
   if (a.part) {
@@ -379,7 +359,7 @@ __device__ __forceinline__ void st_enc_fwd(const StEncFwdArgs& a) {
   float t[HELD ? EPT : 4];
 
   auto load_t = [&](int i, float (&tv)[4]) {
-    st_load4<AL>(x, i, n, tv);
+    c4_load<AL>(x, i, n, tv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) tv[j] = st_lrelu(tv[j] + bias);
   };
@@ -412,7 +392,7 @@ __device__ __forceinline__ void st_enc_fwd(const StEncFwdArgs& a) {
     if constexpr (BL) {
       auto xn_at = [&](int q) { return (st_lrelu(x[q] + bias) - m) * r; };  // (the expression the plain form stores)
       auto xn_at4 = [&](int q, float(&c)[4]) {
-        st_load4<true>(x, q, n, c);
+        c4_load<true>(x, q, n, c);
 #pragma unroll
         for (int j = 0; j < 4; ++j) c[j] = (st_lrelu(c[j] + bias) - m) * r;
       };
@@ -422,7 +402,7 @@ __device__ __forceinline__ void st_enc_fwd(const StEncFwdArgs& a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) yv[j] = ((HELD ? t[4 * k + j] : tv[j]) - m) * r;
     }
-    st_store4<AL>(xn, i, n, yv);
+    c4_store<AL>(xn, i, n, yv);
   });
   if (tid == 0) a.mean[plane] = m, a.std[plane] = (float)sqrt(v);
 }
@@ -460,14 +440,14 @@ __device__ __forceinline__ void st_enc_bwd(const StEncBwdArgs& a) {
     if constexpr (BL)
       st_blur4_of<AL>(dxn, i, n, a.H, a.W, gv);
     else
-      st_load4<AL>(dxn, i, n, gv);
+      c4_load<AL>(dxn, i, n, gv);
   };
 
   float s1 = 0.f, s2 = 0.f;
   if (HELD || dxn) {
     st_chunks<NT, EPT>(n, tid, [&](int k, int i) {
       float xv[4], gv[4] = {0.f, 0.f, 0.f, 0.f};
-      st_load4<AL>(x, i, n, xv);
+      c4_load<AL>(x, i, n, xv);
       if (dxn) load_g(i, gv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -488,7 +468,7 @@ __device__ __forceinline__ void st_enc_bwd(const StEncBwdArgs& a) {
   st_chunks<NT, EPT>(n, tid, [&](int k, int i) {
     float xv[4], gv[4] = {0.f, 0.f, 0.f, 0.f}, ov[4];
     if (!HELD) {
-      st_load4<AL>(x, i, n, xv);
+      c4_load<AL>(x, i, n, xv);
       if (dxn) load_g(i, gv);
     }
 #pragma unroll
@@ -501,7 +481,7 @@ __device__ __forceinline__ void st_enc_bwd(const StEncBwdArgs& a) {
       p1 += dp;
       ov[j] = dp;
     }
-    if (dx) st_store4<AL>(dx, i, n, ov);
+    if (dx) c4_store<AL>(dx, i, n, ov);
   });
   if (a.part) {
     const double P1 = block_sum<NT>((double)p1, red);
@@ -532,18 +512,6 @@ static int st_check_shape(int B, int C, int H, int W) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (long long)H * W < 2) return SIVAE_ERR_SHAPE;
   if ((long long)B * C > 0x7fffffffLL || (long long)H * W > 0x3fffffffLL) return SIVAE_ERR_RANGE;
   return SIVAE_OK;
-}
-
-static bool st_al16(int HW, std::initializer_list<const void*> ptrs) {
-  if (HW % 4) return false;
-  for (const void* p : ptrs)
-    if (p && sivae_misaligned(p, 16)) return false;
-  return true;
-}
-static bool st_al4(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (p && sivae_misaligned(p, 4)) return false;
-  return true;
 }
 
 static void st_mode0_consts(int layer, float* c1, float* c2, float* c3) {
@@ -590,12 +558,12 @@ static int st_dec_fwd_host(bool blur, const float* x, const float* noise, const 
   const int rc = st_check_shape(B, C, H, W);
   if (rc != SIVAE_OK) return rc;
   if (layer < 0 || !(eps >= 0.f)) return SIVAE_ERR_SHAPE;
-  if (!st_al4({x, noise, noise_weight, bias, style, y, mean, rstd})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({x, noise, noise_weight, bias, style, y, mean, rstd})) return SIVAE_ERR_SHAPE;
   const int HW = H * W;
   StDecFwdArgs a = {x, mode ? noise : nullptr, noise_weight, bias, style, y, mean, rstd, C, HW, mode, eps, 0.f, 0.f, 0.f,
                     H, W};
   st_mode0_consts(layer, &a.c1, &a.c2, &a.c3);
-  const bool al = st_al16(HW, {x, a.noise, y});
+  const bool al = c4_al16(HW, {x, a.noise, y});
   if (blur)
     ST_DISPATCH_FWD(style_dec_blur_fwd_kernel, HW, al, (long long)B * C, stream, a);
   else
@@ -634,7 +602,7 @@ static int st_dec_bwd_host(bool blur, const float* dy, const float* x, const flo
   const int rc = st_check_shape(B, C, H, W);
   if (rc != SIVAE_OK) return rc;
   if (layer < 0) return SIVAE_ERR_SHAPE;
-  if (!st_al4({dy, x, noise, noise_weight, bias, style, mean, rstd, dx, dnoise_weight, dbias, dstyle}))
+  if (!c4_al4({dy, x, noise, noise_weight, bias, style, mean, rstd, dx, dnoise_weight, dbias, dstyle}))
     return SIVAE_ERR_SHAPE;
   const bool sums = dbias || dnoise_weight;
   if (sums && (!workspace || sivae_misaligned(workspace, 8) || workspace_bytes < sivae_style_dec_bwd_workspace_bytes(B, C)))
@@ -645,7 +613,7 @@ static int st_dec_bwd_host(bool blur, const float* dy, const float* x, const flo
                     sums ? static_cast<double*>(workspace) : nullptr, C, HW, mode, B * C, 0.f, 0.f, 0.f,
                     H, W, sivae_style_dec_blur_bwd_fused(H, W)};
   st_mode0_consts(layer, &a.c1, &a.c2, &a.c3);
-  const bool al = st_al16(HW, {dy, x, a.noise, dx});
+  const bool al = c4_al16(HW, {dy, x, a.noise, dx});
   if (blur)
     ST_DISPATCH_BWD(style_dec_blur_bwd_kernel, HW, al, (long long)B * C, stream, a);
   else
@@ -678,10 +646,10 @@ static int st_enc_fwd_host(bool blur, const float* x, const float* bias, float* 
   const int rc = st_check_shape(B, C, H, W);
   if (rc != SIVAE_OK) return rc;
   if (!(eps >= 0.f)) return SIVAE_ERR_SHAPE;
-  if (!st_al4({x, bias, xn, mean, stddev})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({x, bias, xn, mean, stddev})) return SIVAE_ERR_SHAPE;
   const int HW = H * W;
   const StEncFwdArgs a = {x, bias, xn, mean, stddev, C, HW, eps, H, W};
-  const bool al = st_al16(HW, {x, xn});
+  const bool al = c4_al16(HW, {x, xn});
   if (blur)
     ST_DISPATCH_FWD(style_enc_blur_fwd_kernel, HW, al, (long long)B * C, stream, a);
   else
@@ -710,14 +678,14 @@ static int st_enc_bwd_host(bool blur, const float* dxn, const float* dmean, cons
   const int rc = st_check_shape(B, C, H, W);
   if (rc != SIVAE_OK) return rc;
   if (!(eps >= 0.f)) return SIVAE_ERR_SHAPE;
-  if (!st_al4({dxn, dmean, dstd, x, bias, mean, stddev, dx, dbias})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({dxn, dmean, dstd, x, bias, mean, stddev, dx, dbias})) return SIVAE_ERR_SHAPE;
   if (dbias && (!workspace || sivae_misaligned(workspace, 8) || workspace_bytes < sivae_style_enc_bwd_workspace_bytes(B, C)))
     return SIVAE_ERR_WORKSPACE;
   if (!dx && !dbias) return SIVAE_OK;
   const int HW = H * W;
   const StEncBwdArgs a = {dxn, dmean, dstd, x, bias, mean, stddev, dx, dbias ? static_cast<double*>(workspace) : nullptr,
                           C, HW, eps, H, W};
-  const bool al = st_al16(HW, {dxn, x, dx});
+  const bool al = c4_al16(HW, {dxn, x, dx});
   if (blur)
     ST_DISPATCH_BWD(style_enc_blur_bwd_kernel, HW, al, (long long)B * C, stream, a);
   else
@@ -745,7 +713,7 @@ extern "C" int sivae_style_enc_blur_bwd(const float* dbxn, const float* dmean, c
 extern "C" int sivae_style_blur(const float* x, float* y, int B, int C, int H, int W, hipStream_t stream) {
   if (!x || !y) return SIVAE_ERR_NULL;
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return SIVAE_ERR_SHAPE;
-  if (!st_al4({x, y})) return SIVAE_ERR_SHAPE;
+  if (!c4_al4({x, y})) return SIVAE_ERR_SHAPE;
   const size_t total = (size_t)B * C * H * W;
   if (total > 256ull * 0x7fffffffull) return SIVAE_ERR_RANGE;
   hipLaunchKernelGGL(style_blur_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, y, total, H, W);

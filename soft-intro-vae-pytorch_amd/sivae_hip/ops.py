@@ -1364,6 +1364,22 @@ def _require_f64(who, *tensors):
             raise TypeError("sivae_hip.%s: expected float64, got %s" % (who, t.dtype))
 
 
+def _require_f32(who, kernels, *tensors, dtype_first=False, skip_none=True):
+    """what the wrappers of the 4-element-chunk kernels (style.hip, rgb.hip, mapping.hip, multi_tensor.hip) demand of
+    every tensor: on a ROCm device, float32, contiguous.  dtype_first: a wrong dtype is named before a wrong device"""
+    for t in tensors:
+        if t is None and skip_none:
+            continue
+        if not dtype_first:
+            _require_device(who, kernels, t)
+        if t.dtype != torch.float32:
+            raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
+        if dtype_first:
+            _require_device(who, kernels, t)
+        if not t.is_contiguous():
+            raise ValueError("sivae_hip.%s: tensor must be contiguous" % who)
+
+
 def fid_state(d, device):
     """-> (G [d, d], s [d]): a zeroed fp64 moment state (sivae_hip.fid.ActivationStatistics holds one)"""
     if not 1 <= int(d) <= FID_MAX_DIMS:
@@ -1585,14 +1601,7 @@ STYLE_NOISE_NONE, STYLE_NOISE_PER_SAMPLE, STYLE_NOISE_BATCH_CONSTANT = 0, 1, 2
 
 
 def _style_f32(who, *tensors):
-    for t in tensors:
-        if t is None:
-            continue
-        _require_device(who, "style", t)
-        if t.dtype != torch.float32:
-            raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
-        if not t.is_contiguous():
-            raise ValueError("sivae_hip.%s: tensor must be contiguous" % who)
+    _require_f32(who, "style", *tensors)
 
 
 def _style_dims(who, x, bias, style=None, noise=None, noise_weight=None, mode=0):
@@ -1844,14 +1853,7 @@ def style_from_rgb_bwd(dy, img, weight, bias, pool=False, has_other=False, blend
 
 # ------------------------------------------------------------------------------------------------ mapping networks, style assembly (mapping.hip)
 def _map_f32(who, *tensors):
-    for t in tensors:
-        if t is None:
-            continue
-        if t.dtype != torch.float32:  # (dtypes first, so that a wrong one is named as such wherever the tensor is)
-            raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
-        _require_device(who, "mapping", t)
-        if not t.is_contiguous():
-            raise ValueError("sivae_hip.%s: tensor must be contiguous" % who)
+    _require_f32(who, "mapping", *tensors, dtype_first=True)  # (so that a wrong dtype is named as such wherever the tensor is)
 
 
 def _map_rows(who, x, *same):
@@ -1986,11 +1988,7 @@ def _mt_f32(who, lists):
     dev = None
     for ts in zip(*lists):
         for t in ts:
-            _require_device(who, "multi-tensor", t)
-            if t.dtype != torch.float32:
-                raise TypeError("sivae_hip.%s: expected float32, got %s" % (who, t.dtype))
-            if not t.is_contiguous():
-                raise ValueError("sivae_hip.%s: tensor must be contiguous" % who)
+            _require_f32(who, "multi-tensor", t, skip_none=False)
             if t.numel() != ts[0].numel():
                 raise ValueError("sivae_hip.%s: element counts differ: %s against %s"
                                  % (who, tuple(t.shape), tuple(ts[0].shape)))
